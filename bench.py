@@ -18,7 +18,14 @@ configs[4] ("random-action stepping", L = 128, 2^20 envs per GPU over 8 GPUs) is
 
     python bench.py --gpus 8 --workload step --L 128 --batch 1048576
 
-Also measured (reported under "variants"): the rollout with an int8 trajectory and with scattered
+A plain run does what that headline needs and no more: it sets up, warms up, times the K steps and
+prints the line ("variants" empty, the CPU baselines null).  `--dump-outputs DIR` adds DIR/<name>.npy
+(float32): what the last timed step returned -- for the rollout the last step's row of each
+trajectory plus the state / step-count / err buffers the launch leaves, for the step workload the
+in-place state and the per-step outputs -- for a fixed, seeded sample of envs (DIR/rows.npy) where
+all of them would pass 60 MB.  Everything below is measured with `--full` only.
+
+With --full, also measured (reported under "variants"): the rollout with an int8 trajectory and with scattered
 resets, the per-call step API (+ hipGraph), the PPO learner step, config 4's searches (device BFS,
 expansion kernel, host-dedup BFS, owner-partitioned BFS).
 
@@ -30,7 +37,7 @@ torchrun starts the ranks (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the envi
 script itself (children, never an exec) and exits with their status.  Every rank checks that the
 process group it joined has exactly --gpus ranks.
 
-CPU baseline (every N): oracle/np_port.py -- a numpy restatement with the reference's per-env
+CPU baseline (--full, every N): oracle/np_port.py -- a numpy restatement with the reference's per-env
 ACEnv.step call pattern -- one process per host core (bounded at 16), 64 envs each, ~10 s, same
 starting states and action stream, plus the C oracle on one core and on every core.  Measured
 once per run before any rank touches the GPU: by the launcher before it starts the ranks (`--gpus
@@ -330,7 +337,16 @@ def parse_args(argv=None):
                          "without it (exit status 3)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: launcher / process group / line plumbing only (gloo, numpy pass per step)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the CPU baselines, the variants, the "
+                         "byte-counting replays of the step roofline (each can be switched off with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the headline's steps, print the line
+        for k in ("cpu", "step_api", "learner", "graph", "bfs", "search", "desync", "obs8", "config2"):
+            setattr(args, "no_" + k, True)
+    return args
 
 
 def main():
@@ -376,7 +392,100 @@ def per_rank_batch(args, world: int) -> tuple:
 
 
 def _per_rank_rows(rows):
-    return [{"rank": i, "value": r[0], "kernel_ms": r[1], "frac": r[2], "wall_ms": r[3]} for i, r in enumerate(rows)]
+    # frac: NaN (a plain --workload step run, whose bytes are not counted) becomes null
+    return [{"rank": i, "value": r[0], "kernel_ms": r[1], "frac": r[2] if r[2] == r[2] else None, "wall_ms": r[3]}
+            for i, r in enumerate(rows)]
+
+
+DUMP_BUDGET = 60 << 20  # bytes a --dump-outputs directory may hold (float32 values + the row list)
+
+
+def dump_rows(B: int, floats_per_env: int) -> np.ndarray:
+    """the envs whose outputs a dump holds: all B, or as many as fit DUMP_BUDGET at
+    `floats_per_env` float32 values each, drawn once with a fixed seed (sorted; the same rows for
+    the same B and L in every run and every build)"""
+    n = DUMP_BUDGET // (4 * floats_per_env + 8)
+    if B <= n:
+        return np.arange(B, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(B, size=n, replace=False)).astype(np.int64)
+
+
+def sample_outputs(tensors: dict, rows: np.ndarray) -> dict:
+    """rows `rows` of each per-env device tensor, as float32 host arrays (the values are small
+    integers: letters, lengths, flags, rewards of at most 2 L H -- exact in float32)"""
+    import torch
+
+    out = {}
+    for name, t in tensors.items():
+        idx = torch.as_tensor(rows, device=t.device)
+        out[name] = t.index_select(0, idx).to(torch.float32).cpu().numpy()
+    return out
+
+
+def write_outputs(path: str, rank: int, rows: np.ndarray, arrays: dict) -> None:
+    """DIR/<name>.npy for rank 0 (DIR/<name>.rank<r>.npy for the others), plus rows.npy: the env
+    index of each row"""
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    np.save(os.path.join(path, f"rows{sfx}.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def plain_step_head(timed, starts, actions, err, err_count, L: int, K: int, W: int, H: int):
+    """`--workload step` without --full: the headline's walk alone -- W warm-up and K timed per-call
+    steps (in place, same-step autoreset) through the step VecACEnv.step takes at this (B, L).  The
+    bytes of an in-place step depend on its walk and are counted by an untimed replay, so the
+    roofline of this line names the kernel and its time only.  Returns (head, the tensors a caller
+    of the last step holds)."""
+    import torch
+
+    from acx import ops
+
+    B, dev = starts.shape[0], starts.device
+    rew = torch.empty(B, dtype=torch.int32, device=dev)
+    dn = torch.empty(B, dtype=torch.uint8, device=dev)
+    tr = torch.empty(B, dtype=torch.uint8, device=dev)
+    st = starts.clone()
+    cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+    use_len = bool(ops.lengths_step_for(B, L))
+    if use_len:
+        lens = torch.full((B, 2), L, dtype=torch.int32, device=dev)  # (L, L): read whole, once
+        kw = {"lengths_in": True, "reduced": torch.zeros(B, dtype=torch.uint8, device=dev)}
+        kernel = f"acx::step_lengths_kernel<{nw_for(L)},{L if L in (36, 128) else 0},4>"
+        call = "acx_step_lengths_reduced (the env's step, ACMove's lengths in/out, per-row reduced flags)"
+    else:
+        lens = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        kw = {}
+        kernel = ops.step_kernel_name(B, L)
+        call = "acx_step"
+
+    def step(a):
+        ops.step(st, a, state_out=st, reset_state=starts, step_count=cnt, horizon=H, cyclical=True, reward=rew,
+                 done=dn, truncated=tr, lengths=lens, err=err, err_count=err_count, **kw)
+
+    err_count.zero_()
+    for t in range(W):
+        step(actions[t])
+
+    def go():
+        for t in range(K):
+            step(actions[W + t])
+
+    wall, s_k, wall_local = timed(go)
+    head = {
+        "elapsed": wall, "kernel_s": s_k, "wall_local": wall_local, "frac": float("nan"),
+        "roofline": {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
+                     "kernel": kernel, "bytes_per_env_step": None, "launch_bytes": None, "kernel_ms": s_k * 1e3,
+                     "launches": K,
+                     "bytes_note": "not counted: the bytes of an in-place step depend on its walk (--full replays "
+                                   "the timed steps off the clock to count them)"},
+        "workload": (f"random-action stepping (BASELINE configs[4]): per-call {call}, {B} envs/GPU, L={L}, "
+                     f"horizon {H}, cyclical=True, in-place state, same-step autoreset; {K} launches"),
+        "env_errors": int(err_count.item()),
+    }
+    return head, {"state": st, "reward": rew, "done": dn, "truncated": tr, "lengths": lens, "step_count": cnt,
+                  "err": err}
 
 
 def restore(snap, tensors) -> None:
@@ -496,6 +605,9 @@ def dry_run(args, rank: int, local_rank: int, world: int) -> None:
         "cpu_baseline": cpu.get("cpu_baseline"), "cpu_baseline_c_oracle": cpu.get("cpu_baseline_c_oracle"),
         "cpu_baseline_c_oracle_all_cores": cpu.get("cpu_baseline_c_oracle_all_cores"),
     }
+    if args.dump_outputs:
+        rows = dump_rows(B, 1)
+        write_outputs(args.dump_outputs, rank, rows, {"acc": acc[rows]})
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -632,6 +744,14 @@ def run_rank(args):
                          f"acx_rollout launches of <= {T_buf} steps ({n_launch} for K={K})"),
             "env_errors": n_err,
         }
+        if args.dump_outputs:
+            # what the last timed env step returned (its row of each trajectory) and the buffers the
+            # launch leaves to its caller; taken here, before any variant reuses the trajectory buffers
+            last = (K % T_buf or T_buf) - 1
+            rows = dump_rows(B, 4 * L + 5)
+            write_outputs(args.dump_outputs, rank, rows, sample_outputs(
+                {"obs": obs[last], "reward": rew[last], "done": done[last], "truncated": trunc[last],
+                 "state": state, "step_count": count, "err": err}, rows))
         del plans
 
     def desync_variant(start_rows, count0, what):
@@ -751,7 +871,15 @@ def run_rank(args):
                          "kernel": f"acx::rollout_kernel<{nw_for(L)},{L if L in (36, 128) else 0},4,2>"}}
         del obs8, rew8, dn8, tr8, st8, cnt8
 
-    if not args.no_step_api or not rollout_head:
+    if not rollout_head and not args.full:
+        head, outs = plain_step_head(timed, starts, actions, err, err_count, L, K, W, H)
+        if args.dump_outputs:
+            rows = dump_rows(B, 2 * L + 7)
+            write_outputs(args.dump_outputs, rank, rows, sample_outputs(outs, rows))
+        del outs
+
+    dumps = {}  # --full --workload step: each walk's last outputs, sampled when its timed steps end
+    if args.full and (not args.no_step_api or not rollout_head):
         # per-call acx_step API: one launch per env step, state in place in HBM, autoreset
         rew1 = torch.empty(B, dtype=torch.int32, device=dev)
         dn1 = torch.empty(B, dtype=torch.uint8, device=dev)
@@ -781,6 +909,10 @@ def run_rank(args):
         chg = replay_walk(lambda t: step(actions[W + t]), st1, (st1, cnt1, err_count), K, L)["changed"]
         wall_api, s_api, wall_api_local = timed(go_steps)
         n_err_api = int(err_count.item())
+        if args.dump_outputs and not rollout_head:
+            dump_at = dump_rows(B, 2 * L + 7)
+            dumps["step"] = sample_outputs({"state": st1, "reward": rew1, "done": dn1, "truncated": tr1,
+                                            "lengths": lens1, "step_count": cnt1, "err": err}, dump_at)
         # per env-step: state in 8L + action 4 + count in 4 + changed relators x 4L + lengths 8 +
         # reward 4 + done 1 + truncated 1 + count out 4 + err 1 (SURVEY 8d counts full-row
         # writes, 8L out; the in-place kernel skips unchanged relators, PMC-checked r02h)
@@ -844,6 +976,9 @@ def run_rank(args):
             sb_len = rd + wr + 16 + 27 + 2  # + the reduced flag in and out
             wall_len, s_len, wall_len_local = timed(go_steps2)
             n_err_len = int(err_count.item())
+            if args.dump_outputs and not rollout_head:
+                dumps["lengths"] = sample_outputs({"state": st2, "reward": rew1, "done": dn1, "truncated": tr1,
+                                                   "lengths": lens2, "step_count": cnt2, "err": err}, dump_at)
             same = bool(torch.equal(st1, st2))  # both walks took the same W + K steps
             len_kernel = f"acx::step_lengths_kernel<{nw_for(L)},{L if L in (36, 128) else 0},4>"
             a_len = B * sb_len / (s_len / K) / 1e9
@@ -895,6 +1030,10 @@ def run_rank(args):
                              f"in-place state, same-step autoreset; {K} launches"),
                 "env_errors": n_err_len,
             }
+        if dumps:  # the walk that became the headline
+            write_outputs(args.dump_outputs, rank, dump_at,
+                          dumps["lengths" if ops.lengths_step_for(B, L) and same else "step"])
+            dumps.clear()
 
         # the same K per-call steps captured once into a hipGraph (torch.cuda.CUDAGraph over
         # the ctypes launches on the capture stream) and replayed from the timed walk's snapshot:
@@ -1038,6 +1177,7 @@ def run_rank(args):
         "cpu_baseline_c_oracle": cpus.get("cpu_baseline_c_oracle"),
         "cpu_baseline_c_oracle_all_cores": cpus.get("cpu_baseline_c_oracle_all_cores"),
         "variants": variants,
+        "full": args.full,
         "env_errors": head["env_errors"],
     }
     if not args.no_bfs:
@@ -1092,6 +1232,8 @@ def committed_step_traffic(B, L, launch_bytes, kernel):
     rocprofv3 PMC profile of the step workload at this (B, L) and of this kernel, as its
     measured/algorithmic ratio applied to this launch's algorithmic bytes (the changed-relator
     rate, hence the bytes, vary slightly with the walk); or (None, None)"""
+    if launch_bytes is None:  # a plain run does not count the walk's bytes
+        return None, None
     want = kernel.replace(" ", "")
     for tag in profile_tags("step128") + profile_tags("step36"):
         prof = os.path.join(REPO, "profiles", tag[:3], f"{tag}_summary.json")

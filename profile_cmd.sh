@@ -15,7 +15,7 @@ ARGS=("$@")
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- python3 $R/bench.py --no-cpu "${ARGS[@]}" > $OUT/trace_bench.log 2>&1 || exit 1
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o bench --output-format csv -- python3 $R/bench.py --no-cpu "${ARGS[@]}" > $OUT/pmc_fetch.log 2>&1 || exit 2
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o bench --output-format csv -- python3 $R/bench.py --no-cpu "${ARGS[@]}" > $OUT/pmc_write.log 2>&1 || exit 3
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- python3 $R/bench.py --full --no-cpu "${ARGS[@]}" > $OUT/trace_bench.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o bench --output-format csv -- python3 $R/bench.py --full --no-cpu "${ARGS[@]}" > $OUT/pmc_fetch.log 2>&1 || exit 2
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o bench --output-format csv -- python3 $R/bench.py --full --no-cpu "${ARGS[@]}" > $OUT/pmc_write.log 2>&1 || exit 3
 echo profile-done

@@ -51,6 +51,25 @@ def test_one_rank_line_has_the_same_shape():
     assert d["n_gpus"] == 1 and d["world_size_seen"] == 1 and len(d["per_rank"]) == 1
 
 
+def test_plain_run_skips_the_cpu_baselines_and_dump_outputs_repeats(tmp_path):
+    """Without --full the line carries no CPU baseline (nothing beside the headline is measured);
+    --dump-outputs DIR writes float32 arrays that are the same from run to run."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        p = subprocess.run([sys.executable, BENCH, "--dry-run", "--steps", "3", "--warmup", "1", "--batch", "256",
+                            "--cpu-seconds", "1", "--dump-outputs", str(tmp_path / name)],
+                           cwd=REPO, capture_output=True, text=True, timeout=120, env=_env())
+        assert p.returncode == 0, p.stderr[-3000:]
+        (d,) = _lines(p.stdout)
+        assert d["steps"] == 3 and d["cpu_baseline"] is None and d["cpu_baseline_c_oracle"] is None
+        dumps.append({f.name: np.load(f) for f in (tmp_path / name).iterdir()})
+    assert sorted(dumps[0]) == ["acc.npy", "rows.npy"] and dumps[0]["acc.npy"].dtype == np.float32
+    assert dumps[0]["acc.npy"].shape == (256,) and dumps[0]["acc.npy"].any()
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -145,7 +164,7 @@ def _check_cpu(d, where):
 def test_launcher_line_carries_cpu_baseline():
     """`bench.py --gpus 2` (the launcher) puts the CPU baselines -- measured on
     the host's cores before any rank started -- into rank 0's line."""
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "0",
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--steps", "2", "--warmup", "0",
                         "--batch", "256", "--cpu-seconds", "1"], cwd=REPO, capture_output=True, text=True,
                        timeout=240, env=_env())
     assert p.returncode == 0, p.stderr[-3000:]
@@ -159,7 +178,7 @@ def test_torchrun_line_carries_cpu_baseline():
     the process group."""
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), BENCH, "--gpus", "2",
-                        "--dry-run", "--steps", "2", "--warmup", "0", "--batch", "256", "--cpu-seconds", "1"],
+                        "--dry-run", "--full", "--steps", "2", "--warmup", "0", "--batch", "256", "--cpu-seconds", "1"],
                        cwd=REPO, capture_output=True, text=True, timeout=240, env=_env())
     assert p.returncode == 0, p.stderr[-3000:]
     (d,) = _lines(p.stdout)

@@ -24,7 +24,7 @@ def _bench(*args, timeout=240, env=None):
 
 
 def test_bench_line_multi_launch_small_batch():
-    d = _bench("--batch", "8192", "--steps", "210", "--warmup", "3", "--no-cpu", "--no-bfs", "--no-learner",
+    d = _bench("--full", "--batch", "8192", "--steps", "210", "--warmup", "3", "--no-cpu", "--no-bfs", "--no-learner",
                "--no-graph", "--no-search")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
@@ -50,8 +50,8 @@ def test_bench_line_short_launch_reads_int32_ids():
 def test_bench_step_workload_headline():
     # config 5's shape (--workload step) at a small batch: the per-call step API is the headline
     # (the lengths-carrying acx_step_lengths; acx_step on the same walk is a variant)
-    d = _bench("--workload", "step", "--L", "128", "--batch", "8192", "--steps", "12", "--warmup", "2", "--no-cpu",
-               "--no-bfs", "--no-learner", "--no-search")
+    d = _bench("--full", "--workload", "step", "--L", "128", "--batch", "8192", "--steps", "12", "--warmup", "2",
+               "--no-cpu", "--no-bfs", "--no-learner", "--no-search")
     assert d["n_gpus"] == 1 and d["world_size_seen"] == 1 and d["env_errors"] == 0
     assert d["roofline"]["kernel"] == "acx::step_lengths_kernel<8,128,4>" and d["roofline"]["launches"] == 12
     v = d["variants"]
@@ -61,6 +61,31 @@ def test_bench_step_workload_headline():
     assert "rollout_obs_int8" not in d["variants"] and "step_api_hipgraph" in d["variants"]
     r8 = d["variants"]["stepping_rollout_obs_int8"]
     assert r8["env_errors"] == 0 and r8["value"] > 0 and r8["roofline"]["kernel"] == "acx::rollout_kernel<8,128,4,2>"
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    # no --full: no variants, no CPU baselines; --dump-outputs writes the last timed step's outputs
+    # (all 4096 envs fit) as float32 arrays, a caller's view of the launch
+    import numpy as np
+
+    out = tmp_path / "dump"
+    d = _bench("--batch", "4096", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out))
+    assert d["full"] is False and d["variants"] == {} and d["cpu_baseline"] is None
+    assert d["steps"] == 20 and d["env_errors"] == 0 and d["roofline"]["launches"] == 1
+    assert abs(d["value"] - 4096 * 20 / (d["ms_per_step"] * 20 / 1e3)) < 1e-6 * d["value"]
+    got = {p.name: np.load(p) for p in out.iterdir()}
+    assert sorted(got) == sorted(n + ".npy" for n in ("rows", "obs", "reward", "done", "truncated", "state",
+                                                      "step_count", "err"))
+    assert np.array_equal(got["rows.npy"], np.arange(4096))
+    assert all(a.dtype == np.float32 for n, a in got.items() if n != "rows.npy")
+    assert got["obs.npy"].shape == got["state.npy"].shape == (4096, 72)
+    assert all(got[n + ".npy"].shape == (4096,) for n in ("reward", "done", "truncated", "step_count", "err"))
+    assert set(np.unique(got["obs.npy"])) <= {-2.0, -1.0, 0.0, 1.0, 2.0} and not got["err.npy"].any()
+    # 25 steps from step count 0 under horizon 200: no truncation yet; same-step autoreset puts a
+    # done env's count back to 0
+    assert not got["truncated.npy"].any()
+    assert (got["step_count.npy"] <= 25).all() and (got["step_count.npy"][got["done.npy"] == 1] == 0).all()
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
 
 
 def test_bench_launcher_two_ranks_gloo_one_gpu():

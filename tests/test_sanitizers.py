@@ -115,7 +115,10 @@ def test_oracle_under_asan_ubsan(tmp_path):
                              check=True).stdout.strip()
     env = dict(os.environ, LD_PRELOAD=asan_rt, ACX_ORACLE_LIB=os.path.join(REPO, "oracle", "liboracle_asan.so"),
                ASAN_OPTIONS="halt_on_error=1:exitcode=66:detect_leaks=0", UBSAN_OPTIONS=SAN_ENV["UBSAN_OPTIONS"])
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider",
+    # --rootdir: without it pytest takes the common ancestor of the working directory (tmp_path) and
+    # the test file as its root and collects downwards from there, through directories that are
+    # not the project's (and need not be readable)
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider", "--rootdir", REPO,
                         os.path.join(REPO, "tests", "test_oracle.py")], capture_output=True, text=True, env=env,
                        cwd=str(tmp_path), timeout=900)
     reports = [m for m in REPORT_MARKERS if m in r.stdout + r.stderr]

@@ -52,10 +52,10 @@ for step in "$@"; do
         timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke-ok')" \
             > $OUT/${TAG}_smoke.log 2>&1 || exit 2
         tail -2 $OUT/${TAG}_smoke.log ;;
-    bench) timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 3 ;;
-    benchq) timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 --no-cpu > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 3 ;;
+    bench) timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 3 ;;
+    benchq) timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 --no-cpu > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 3 ;;
     config5)
-        timeout -k 10 400 python -u bench.py --workload step --L 128 --no-cpu --no-bfs --no-search \
+        timeout -k 10 400 python -u bench.py --full --workload step --L 128 --no-cpu --no-bfs --no-search \
             > $OUT/${TAG}_config5.json 2> $OUT/${TAG}_config5.err || exit 4 ;;
     config2) timeout -k 10 300 python -u tools/bench_configs.py > $OUT/${TAG}_config2.json 2> $OUT/${TAG}_config2.err || exit 5 ;;
     learner) timeout -k 10 300 python -u tools/learner_probe.py > $OUT/${TAG}_learner_probe.json 2> $OUT/${TAG}_learner_probe.err || exit 6 ;;
