@@ -15,6 +15,8 @@
 
 #include "acx.h"
 
+#include "acx_cur_layout.h"
+
 namespace acx {
 namespace cur {
 
@@ -172,13 +174,10 @@ using namespace acx::cur;
 extern "C" {
 
 int64_t acx_internal_curriculum_fused_offset(int64_t B);
-#define ACX_CUR_ARRIVE_STRIDE 32  // as acx_kernels.hip's CurLayout
 int64_t acx_curriculum_workspace(int64_t B) {
     if (B < 0) return 0;
-    const int64_t tiles = (B + WAVE - 1) / WAVE, groups = (tiles + WAVE - 1) / WAVE;
-    // acx_learner_step's part: [0] sequence number, [1, 2] base, tile counts, group totals, and
-    // the groups' arrival words ACX_CUR_ARRIVE_STRIDE apart (acx_kernels.hip, CurLayout)
-    return acx_internal_curriculum_fused_offset(B) + 2 * (3 + tiles + groups + groups * ACX_CUR_ARRIVE_STRIDE);
+    // this file's part, then acx_learner_step's (uint64 words laid out by acx_cur_layout.h)
+    return acx_internal_curriculum_fused_offset(B) + 2 * acx::cur_layout::words(B);
 }
 
 int acx_curriculum_assign(const uint8_t* done, const uint8_t* truncated, const int32_t* curriculum_states,
@@ -205,11 +204,9 @@ int acx_curriculum_assign(const uint8_t* done, const uint8_t* truncated, const i
 }
 
 // acx_learner_step (acx_kernels.hip) ranks the finished envs inside its step kernel with a
-// look-back over per-64-env-tile status words; its part of the workspace starts after this
-// file's (next_index copy + per-block counts), so either call may use one workspace:
-// uint64 words from off: the launch sequence number, the base, one reserved word, one count per
-// 64-env tile, then per group of 64 tiles its total and its arrival word (acx_kernels.hip
-// cur_publish / cur_prefix).
+// look-back over per-64-env-tile status words (acx_kernels.hip: cur_publish / cur_prefix); its
+// part of the workspace (acx_cur_layout.h) starts after this file's (next_index copy + per-block
+// counts), so either call may use one workspace.
 int64_t acx_internal_curriculum_fused_offset(int64_t B) {
     const int64_t own = (B + TPB - 1) / TPB + 2;
     return (own + 1) & ~(int64_t)1;  // 8-byte aligned

@@ -7,10 +7,13 @@
 //     L = 36, so a lane reading "its" row directly would touch 64 lines per load);
 //     in LDS each letter is one int8, rows padded to an odd number of dwords so the
 //     per-lane row reads are bank-conflict free.
-//   * Each lane then packs its two relators into registers, 2 bits per letter
-//     (x=0, x^-1=1, y=2, y^-1=3, so inversion is `code ^ 1`), as little multiword
-//     integers Word<NW> (NW 32-bit words, letter k at bits [2k, 2k+2)).
-//   * A move is O(NW) register work, no per-letter loops:
+//   * Each lane then packs its two relators into registers.  The expansion kernels (expand12*,
+//     canon, unpack_keys) hold a relator at 2 bits per letter (x=0, x^-1=1, y=2, y^-1=3, so
+//     inversion is `code ^ 1`), as little multiword integers Word<NW> (acx_moves.h: NW 32-bit
+//     words, letter k at bits [2k, 2k+2)).  The step and rollout kernels hold it as two bit
+//     planes (acx_planes.h: sign and generator masks, letter k at bit k) and run the same moves
+//     on them.
+//   * A move is O(NW) register work, no per-letter loops (on Word<NW>; the planes likewise):
 //       concatenate r_i <- r_i r_j^{+-1}  (reference ac_moves.py:4-76): the junction
 //         cancellation count is the first non-zero letter of
 //         reverse(r_i) XOR r_j^{+-1} XOR 0x55..  (count-trailing-zeros), the splice is
@@ -22,6 +25,16 @@
 //       cyclic reduction (utils.py:223-232): peel count = first non-zero letter of
 //         w XOR reverse(w) XOR 0x55.. .
 //   * No MFMA: the path is integer/byte work and HBM-bound.
+//
+// This file is the one translation unit of the env-side kernels (build.py compiles it once more
+// per -DACX_PART=n).  Its bottom layer is in headers, one concern each; CodeTile, TileFor, the
+// kernels, the launchers, the part table and the C-ABI are here:
+//   acx_moves.h, acx_planes.h   the word algebra (Word<NW> / bit planes)
+//   acx_tile_io.h               HBM <-> LDS staging helpers and their cache-policy constants
+//   acx_tile_base.h             what FastTile and CodeTile share
+//   acx_tile_fast.h, acx_tile_generic.h   two of the three LDS tile classes
+//   acx_step_args.h             the kernels' argument structs
+//   acx_cur_layout.h            the fused learner's workspace layout
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,932 +44,121 @@
 
 #include "acx.h"
 
+#include "acx_cur_layout.h"
 #include "acx_moves.h"
 #include "acx_planes.h"
+#include "acx_step_args.h"
+#include "acx_tile_base.h"
+#include "acx_tile_fast.h"
+#include "acx_tile_generic.h"
+#include "acx_tile_io.h"
 
 namespace acx {
 
 // ---------------------------------------------------------------------------------
 // LDS staging.  A wave owns a tile of up to 64 consecutive envs.  The tile is moved
 // HBM <-> LDS with coalesced 16-byte (or 8-byte) accesses by all 64 lanes, as int8
-// letters; then each lane packs / unpacks its own row.  Two implementations with one
-// interface:
-//   FastTile   compile-time L with L % 4 == 0 (the L = 36 and L = 128 configs): the LDS
+// letters; then each lane packs / unpacks its own row.  Three implementations with one
+// interface (TileFor picks by L; the helpers they share are in acx_tile_io.h and acx_tile_base.h):
+//   CodeTile   (below) compile-time L >= 64 with L % 8 == 0 (L = 128): one 16-bit slot of 2-bit
+//              codes and a non-zero mask per 4 letters.
+//   FastTile   (acx_tile_fast.h) any other compile-time L with L % 4 == 0 (L = 36): the LDS
 //              tile is the int8 image of the global tile, row stride S dwords with
 //              S = 2 mod 4 so each lane's 8-byte row reads/writes hit distinct bank
 //              pairs; addresses are affine in the chunk index; pack/unpack are SWAR over
 //              4 letters per dword.
-//   GenericTile  runtime L (parity tests at any L <= 128): per-letter pack/unpack.
+//   GenericTile  (acx_tile_generic.h) runtime L (parity tests at any L <= 128): per-letter pack/unpack.
 // Rows holding a value outside {-2..2} are flagged (flags[row]) at load time.
+//
+// The tile interface: what a kernel may use of a Tile ("all": each class implements it for real).
+//   Tile(lds_slice, L), wave_bytes(L)   the wave's slice of dynamic LDS and its size: all
+//   Lr()                       the row's L (compile-time where the class has one): all
+//   PW                         64-bit words per bit plane, for PlaneRegs<PW>: all
+//   load<PIPE, LIVE, NTL, BATCH>(g, R, lane)
+//                              R contiguous global rows -> LDS, flags set: all.  PIPE (software-
+//                              pipelined full tile): CodeTile; FastTile's loop is unrolled anyway,
+//                              GenericTile ignores it.  LIVE (only the chunks inside each relator's
+//                              letters, after set_lim): FastTile, CodeTile; GenericTile reads whole
+//                              rows.  NTL (non-temporal loads): FastTile, CodeTile.  BATCH (loads
+//                              in flight): FastTile
+//   load_block(g, R)           the same by all threads of the block, block-wide barriers:
+//                              FastTile, CodeTile; GenericTile has none (callers test LC)
+//   load_rows(g, rows, R, lane)  only the rows in the wave-uniform mask `rows`: all
+//   PREFETCH_OK, RPI, fetch_rows(g, rows, lane), put_rows(v, rows, apply, lane)
+//                              load_rows in two halves, at most RPI rows: FastTile
+//                              (PREFETCH_OK); CodeTile and GenericTile stub them, never called
+//   pack(lane, regs)           lane's row -> PlaneRegs<PW> or PresRegs<NW>, true if the row is
+//                              outside the domain: all.  pack<LIVE>(lane, PlaneRegs): skips groups
+//                              past every row's live chunks, CodeTile; the others ignore LIVE
+//   unpack(lane, regs), unpack_half(lane, regs, h1)
+//                              registers -> lane's row / its relator h1 only: all
+//   unpack_dirty<LIVE>(lane, regs)
+//                              unpack, returning which relators changed (bit h): FastTile,
+//                              CodeTile (LIVE: CodeTile); GenericTile always returns 3
+//   LIVE_ROWS, set_lim(lane, n0, n1), widen_lim(lane, n0, n1)
+//                              the live chunks of the row's relators, for load<LIVE> and
+//                              store_dirty<LIVE>: FastTile, CodeTile; GenericTile (LIVE_ROWS
+//                              false) stubs them
+//   set_dirty(lane, m), store_dirty<NT, LIVE>(g, R, lane, fallback2)
+//                              in-place store of the changed relators only: FastTile, CodeTile;
+//                              GenericTile stores every row
+//   store<FB, NT, F32>(g, gpitch, R, fallback, fpitch, lane, fallback2, skip)
+//                              LDS -> global rows of any pitch, flagged rows from their fallback
+//                              row (FB), as float32 (F32), rows in `skip` left out: all
+//   store_rows<NT>(g, R, lane), store_rows_i8<NT>(g, R, lane)
+//                              LDS -> contiguous rows as int32 / int8 letters: all (FastTile's
+//                              store_rows also takes a chunk range)
+//   NT_STEP_LOADS              the step kernels' NTL choice (see ld_tile): all
+//   restore_flags(lane, code), flag_rows(lane, code), flags[], letter(r, k)
+//                              the rows' fallback codes set / added by the kernel, and one letter
+//                              of the LDS image (store_rows_i8_fb): all
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// int32 letter -> int8; values outside {-2..2} become 0x7F and set `bad`
-__device__ __forceinline__ uint32_t to_i8(int32_t v, bool& bad) {
-    const bool ok = (uint32_t)(v + 2) <= 4u;
-    bad |= !ok;
-    return ok ? ((uint32_t)v & 0xffu) : 0x7fu;
-}
-
-__device__ __forceinline__ int4 widen4(uint32_t p) {
-    int4 x;
-    x.x = (int32_t)(int8_t)(p & 0xffu);
-    x.y = (int32_t)(int8_t)((p >> 8) & 0xffu);
-    x.z = (int32_t)(int8_t)((p >> 16) & 0xffu);
-    x.w = (int32_t)(int8_t)(p >> 24);
-    return x;
-}
-
-
-constexpr int STAGE_UNROLL = 8;
-// Cache-policy choices, each settled by an interleaved A/B on one buffer set (the measurements
-// are cited where each is used; the losing variants live in commit history, not here):
-//   * the rollout's write-once trajectory: non-temporal / sc1 stores (1.4 % faster at T = 200);
-//     its reward/done/truncated stay plain (non-temporal cost 0.4 %);
-//   * the in-place step's write-back of changed relators: non-temporal (L = 36) or an sc1
-//     buffer store (L = 128); whole output rows stay plain;
-//   * tile loads: non-temporal for the L = 128 step and the rollout's state in, plain for the
-//     L = 36 step; expand12's parent loads and key stores non-temporal.
-constexpr bool NT_OBS = true;
-
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ void st16(int4* p, const int4& v) {
-    if constexpr (NT) {
-        const v4i_t x = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(x, reinterpret_cast<v4i_t*>(p));
-    } else {
-        *p = v;
-    }
-}
-// 16 bytes of a row: int32 letters, or (F32) the same letters as float32 (the PPO learner's
-// observation buffer, training.py:151-153)
-template <bool NT, bool F32>
-__device__ __forceinline__ void out16(int4* p, const int4& v) {
-    if constexpr (F32) {
-        typedef float v4f_t __attribute__((ext_vector_type(4)));
-        const v4f_t f = {(float)v.x, (float)v.y, (float)v.z, (float)v.w};
-        if constexpr (NT) __builtin_nontemporal_store(f, reinterpret_cast<v4f_t*>(p));
-        else *reinterpret_cast<v4f_t*>(p) = f;
-    } else {
-        st16<NT>(p, v);
-    }
-}
-template <bool F32>
-__device__ __forceinline__ void out8(int2* p, const int2& v) {
-    if constexpr (F32) {
-        float2 f;
-        f.x = (float)v.x;
-        f.y = (float)v.y;
-        *reinterpret_cast<float2*>(p) = f;
-    } else {
-        *p = v;
-    }
-}
-template <bool NT, class T>
-__device__ __forceinline__ void st_scalar(T* p, T v) {
-    if constexpr (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-
-// 4 int8 letters (one dword) -> 8-bit code field (2 bits per letter, x=0 X=1 y=2 Y=3, zero
-// letters -> 0) and a 4-bit non-zero mask.  A letter's low 3 bits index an 8-entry byte table
-// (v_perm_b32: 0 -> 0, 1 (x), 2 (y), 6 (Y = -2), 7 (X = -1)), and v_dot4_u32_u8 folds the four
-// per-byte results into their fields (weights 1, 4, 16, 64 for the codes, 1, 2, 4, 8 for the
-// mask): 6 VALU where a shift-and-mask SWAR took ~16.  Bytes outside {0, +-1, +-2} give
-// arbitrary codes (their rows are flagged and never decoded from the tile); 0x7F, to_i8's
-// out-of-domain byte, counts as non-zero.
-__device__ __forceinline__ void pack4_codes(uint32_t d, uint32_t& c8, uint32_t& nz4) {
-    const uint32_t m = d & 0x07070707u;
-    const uint32_t codes = __builtin_amdgcn_perm(0x01030000u, 0x00020000u, m);
-    const uint32_t nz = __builtin_amdgcn_perm(0x01010101u, 0x01010100u, m);
-    c8 = __builtin_amdgcn_udot4(codes, 0x40100401u, 0u, false);
-    nz4 = __builtin_amdgcn_udot4(nz, 0x08040201u, 0u, false);
-}
-
-// Non-temporal stores for the in-place step's write-back of changed relators: nothing reads
-// those lines again inside the launch, and plain stores kept them in L2 beside the tile loads
-// (same buffers: L = 128 0.2727 -> 0.2581 ms, lengths-carrying 0.2302 -> 0.2102, L = 36
-// 0.0742 -> 0.0697; profiles/r04/r04z_ab_nt*.json).  Whole output rows (the out-of-place step,
-// the rollout's final state, canonicalized rows, expanded children) stay plain: non-temporal
-// made the rollout slower (K = 20 int32 1.332 -> 1.351 ms, int8 0.447 -> 0.477; its next launch
-// reads that state) and expand12's children no faster (0.778 -> 0.772 ms).
-constexpr bool NT_WRITEBACK = true;
-constexpr bool NT_STATE = false;
-// Buffer-instruction cache policies (gfx950 cpol bits: sc0 1, nt 2, sc1 16).
-// The L = 128 in-place step's write-back (CodeTile): sc1, same buffers: lengths-carrying 0.1993 ->
-// 0.1791 ms, acx_step 0.2423 -> 0.2182 against nt; nt + sc1 0.1989 (profiles/r04/r04s_ab_wb_cpol.json).
-// FastTile (L = 36) keeps the global non-temporal write-back: sc1 measured 0.0757 vs nt 0.0698 ms
-// per 2^20-env step (r04s_ab_wb36_cpol.json).
-constexpr int WB_CPOL = 16;
-// The rollout's int32 trajectory stores (full tiles): sc1 (the line is not kept in the XCD's L2):
-// same buffers, K = 20 on Samsung boxes 1.2377 -> 1.2059 and 1.3241 -> 1.3027 ms against nt,
-// plain 1.2267 / 1.3195; K = 200 within 0.3 % (profiles/r04/r04s_ab_obs_cpol*.json).  The int8
-// trajectory keeps global non-temporal stores: K = 20 0.4626 ms vs sc1 0.4862, plain 0.494
-// (r04s_ab_obs8_cpol.json).
-constexpr int OBS_CPOL = 16;
-// expand12's parent loads and packed-key stores non-temporal (keys as 16-B stores): same buffers,
-// 4M parents (profiles/r04/r04z_ab_keys.json): 0.4246 ms (0.71 of 8 TB/s) -> 0.380 ms (0.79) with
-// both; the loads alone 0.4085, the stores alone 0.5101 (slower); the children kernel unchanged
-constexpr bool NT_EXPAND_LOADS = true;
-constexpr bool NT_KEYS = true;
-// Non-temporal tile loads (NTL): the state rows are read once per launch.  Taken where it
-// measured faster (same buffers, profiles/r04/r04z_ab_ld*.json): the L = 128 step (CodeTile:
-// 0.2587 -> 0.2432 ms, lengths-carrying 0.2105 -> 0.1991) and the rollout's state in (int8
-// trajectory 0.4635 -> 0.4402 ms, int32 1.3235 -> 1.3131); not the L = 36 step, whose write-back
-// of relators that are not sector-aligned (288-B rows) then went 0.0699 -> 0.0944 ms.
-template <bool NT>
-__device__ __forceinline__ int4 ld_tile(const int4* p) {
-    if constexpr (NT) {
-        const v4i_t x = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p));
-        return make_int4(x[0], x[1], x[2], x[3]);
-    } else {
-        return *p;
-    }
-}
-constexpr int tile_cpol(bool nt) { return nt ? 2 : 0; }  // buffer-load cache policy: nt (gfx94x/950 bits)
-// 16 bytes of a row (4 int32 letters) -> the dword of their low bytes (2 v_perm_b32 + or);
-// bad = a letter outside {-2..2} (max / min of the four).  A bad chunk's bytes are arbitrary:
-// its row is flagged and never decoded from the tile.
-__device__ __forceinline__ uint32_t chunk_i8(const int4& v, bool& bad) {
-    const uint32_t lo = __builtin_amdgcn_perm((uint32_t)v.y, (uint32_t)v.x, 0x0c0c0400u);  // x.b0, y.b0
-    const uint32_t hi = __builtin_amdgcn_perm((uint32_t)v.w, (uint32_t)v.z, 0x04000c0cu);  // z.b0, w.b0
-    const int mx = max(max(v.x, v.y), max(v.z, v.w));
-    const int mn = min(min(v.x, v.y), min(v.z, v.w));
-    bad = mx > 2 || mn < -2;
-    return lo | hi;
-}
-
-// chunk_i8 with the range test folded into a running max / min of the letters (two v_max3 and
-// two v_min3 per chunk, no compare): some letter is outside {-2..2} <=> mx > 2 or mn < -2
-__device__ __forceinline__ uint32_t chunk_i8_acc(const int4& v, int& mx, int& mn) {
-    const uint32_t lo = __builtin_amdgcn_perm((uint32_t)v.y, (uint32_t)v.x, 0x0c0c0400u);
-    const uint32_t hi = __builtin_amdgcn_perm((uint32_t)v.w, (uint32_t)v.z, 0x04000c0cu);
-    mx = max(max(mx, v.x), v.y);
-    mx = max(max(mx, v.z), v.w);
-    mn = min(min(mn, v.x), v.y);
-    mn = min(min(mn, v.z), v.w);
-    return lo | hi;
-}
-
-// 8-bit code field -> 4 int8 letters, the first s/8 kept (s = 8m, m = 0..4), the rest zero.
-// The four 2-bit codes are spread to one per byte (two shift-or-mask rounds); a byte past m
-// gets selector bit 2 set, so one v_perm_b32 reads either the letter table {1,-1,2,-2}
-// (src1 bytes 0..3) or zero (src0 bytes 4..7).  ~7 full-rate VALU ops per 4 letters.
-__device__ __forceinline__ uint32_t codes_to_i8x4(uint32_t c8, uint32_t s) {
-    uint32_t x = (c8 | (c8 << 12)) & 0x000F000Fu;
-    x = (x | (x << 6)) & 0x03030303u;
-    const uint32_t z = (uint32_t)(0x04040404ull << s);  // 0x04 in bytes >= m (s = 32 -> none)
-    return __builtin_amdgcn_perm(0u, 0xFE02FF01u, x | z);
-}
-__device__ __forceinline__ uint32_t clamp_bits(int s) { return (uint32_t)(s < 0 ? 0 : (s > 32 ? 32 : s)); }
-
-// Rows outside the packed domain (a letter not in {-2..2}, a zero inside a relator) cannot be
-// held in the LDS image; the stores copy their exact int32 values from a fallback row instead,
-// chosen per row by its code in the tile's flags[]:
-//   FB_IN     the row the kernel loaded (state_in / the rollout's input state)
-//   FB_RESET  the env's starting row (reset_state): an autoreset to an out-of-domain row
-constexpr uint32_t FB_IN = 1u, FB_RESET = 2u;
-__device__ __forceinline__ const int32_t* fb_src(uint32_t code, const int32_t* fb_in, const int32_t* fb_reset) {
-    return code == FB_RESET ? fb_reset : fb_in;
-}
-
-template <int NW, int LC>
-struct FastTile {
-    static_assert(LC > 0 && LC % 4 == 0, "FastTile needs a compile-time L multiple of 4");
-    static constexpr int L = LC;
-    static constexpr int twoL = 2 * LC;
-    static constexpr int CPR = LC / 2;  // 16-byte chunks (4 letters) per row
-    static constexpr int S = (CPR % 4 == 2) ? CPR : CPR + 2;  // LDS row stride (dwords), = 2 mod 4
-    static constexpr int HALF = CPR / 2;  // dwords per relator
-    static_assert(S % 4 == 2, "row stride must be 2 mod 4 dwords");
-    static constexpr int LOAD_BATCH = 6;
-
-    uint32_t* lds;
-    uint8_t* flags;
-    uint8_t* dirty;         // per row: bit h = relator h differs from the loaded row (store_dirty)
-    uint8_t* lim;           // per row and relator, lengths-carrying step: live 16-byte chunks (lim[2r + h])
-    bool tile_bad = false;  // wave-uniform: some row of the last load was flagged
-
-    static __host__ __device__ constexpr size_t wave_bytes(int) { return (size_t)WAVE * S * 4 + 4 * WAVE; }
-    // per-row fallback codes (FB_* below) replacing whatever the loads left in flags[]; the
-    // flagged rows of store<true> / store_dirty / store_rows_i8_fb copy their fallback row
-    __device__ __forceinline__ void restore_flags(int lane, uint32_t code) {
-        flags[lane] = (uint8_t)code;
-        tile_bad = __any(code != 0u);
-        wave_sync();
-    }
-    // additionally flag the rows of lanes with code != 0
-    __device__ __forceinline__ void flag_rows(int lane, uint32_t code) {
-        if (code) flags[lane] = (uint8_t)code;
-        tile_bad = tile_bad || __any(code != 0u);
-    }
-    // int8 letter k of row r of the LDS image (the rare fallback stores)
-    __device__ __forceinline__ int32_t letter(int r, int k) const { return row(r)[k]; }
-    __device__ __forceinline__ FastTile(char* base, int) {
-        lds = reinterpret_cast<uint32_t*>(base);
-        flags = reinterpret_cast<uint8_t*>(base + WAVE * S * 4);
-        dirty = flags + WAVE;
-        lim = flags + 2 * WAVE;
-    }
-    // lengths-carrying step: row `lane` has relators of n0 / n1 letters -> its live chunk counts
-    __device__ __forceinline__ void set_lim(int lane, int n0, int n1) const {
-        lim[2 * lane] = (uint8_t)live_chunks(n0);
-        lim[2 * lane + 1] = (uint8_t)live_chunks(n1);
-    }
-    __device__ __forceinline__ static int live_chunks(int n) { return n <= 0 ? 0 : n >= L ? HALF : (n + 3) >> 2; }
-    // before the store: the live chunks of the row's old (set_lim) or new letters n0 / n1
-    __device__ __forceinline__ void widen_lim(int lane, int n0, int n1) const {
-        const int a = live_chunks(n0), b = live_chunks(n1);
-        if (a > lim[2 * lane]) lim[2 * lane] = (uint8_t)a;
-        if (b > lim[2 * lane + 1]) lim[2 * lane + 1] = (uint8_t)b;
-    }
-    // chunk k (< CPR) of row r is live (inside its relator's letters)
-    __device__ __forceinline__ bool live(int r, int k) const {
-        const int h = k >= HALF ? 1 : 0;
-        return k - h * HALF < lim[2 * r + h];
-    }
-    __device__ __forceinline__ int Lr() const { return L; }
-    __device__ __forceinline__ int8_t* row(int r) const { return reinterpret_cast<int8_t*>(lds + r * S); }
-
-    // LDS dword index of chunk c = lane + 64u (compile-time u)
-    __device__ __forceinline__ static int lds_index(int ln, int u) {
-        if constexpr (S == CPR) return ln + WAVE * u;           // unpadded: LDS image is flat
-        else if constexpr (CPR == WAVE) return u * S + ln;      // one row per wave-instruction
-        else {
-            const int c = ln + WAVE * u;
-            const int r = c / CPR;
-            return r * S + (c - r * CPR);
-        }
-    }
-
-    // global rows (contiguous, 2L int32 each) -> LDS (PIPE: see CodeTile::load; this full-tile
-    // loop is unrolled already).  LIVE (the lengths-carrying step; lim[] set for every row): only
-    // the chunks inside each relator's letters are read, the rest of the image is zero (the rows
-    // are canonical: letters, then zero padding)
-    template <bool PIPE = false, bool LIVE = false, bool NTL = false, int BATCH = 0>
-    __device__ __forceinline__ void load(const int32_t* __restrict__ g, int R, int lane) {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));  // keep the address math here (no hoisting into the caller)
-        flags[ln] = 0;
-        wave_sync();
-        const int nc = R * CPR;
-        const int4* src = reinterpret_cast<const int4*>(g) + ln;
-        bool any_bad = false;
-        if (R == WAVE) {  // full tile (wave-uniform): unguarded, LOAD_BATCH loads in flight
-            // LIVE: loads through a buffer descriptor over the tile's rows, a dead chunk at an
-            // out-of-range offset (zeros, nothing read): no load under a branch (see CodeTile::load)
-            const uint64_t gb = reinterpret_cast<uint64_t>(g);
-            const uint32_t glo = __builtin_amdgcn_readfirstlane((uint32_t)gb);
-            const uint32_t ghi = __builtin_amdgcn_readfirstlane((uint32_t)(gb >> 32));
-            const __amdgpu_buffer_rsrc_t rows = __builtin_amdgcn_make_buffer_rsrc(
-                reinterpret_cast<void*>(((uint64_t)ghi << 32) | glo), (short)0, WAVE * CPR * 16, 0x00020000);
-            // BATCH (the small-batch step instance): loads in flight per batch, up to the whole
-            // tile row (CPR: one round trip); LOAD_BATCH otherwise (the 8-wave/SIMD VGPR budget)
-            constexpr int LB = BATCH > 0 ? BATCH : LOAD_BATCH;
-#pragma unroll
-            for (int u0 = 0; u0 < CPR; u0 += LB) {
-                int4 v[LB];
-                bool lv[LB];
-#pragma unroll
-                for (int u = 0; u < LB; ++u) {
-                    if (u0 + u >= CPR) continue;
-                    const int c = ln + (u0 + u) * WAVE;
-                    lv[u] = true;
-                    if constexpr (LIVE) {
-                        const uint32_t off = live(c / CPR, c % CPR) ? (uint32_t)c * 16u : 0x80000000u;
-                        const auto x = __builtin_amdgcn_raw_buffer_load_b128(rows, off, 0, tile_cpol(NTL));
-                        v[u] = make_int4((int)x[0], (int)x[1], (int)x[2], (int)x[3]);
-                    } else {
-                        v[u] = ld_tile<NTL>(src + (u0 + u) * WAVE);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < LB; ++u) {
-                    if (u0 + u >= CPR) continue;
-                    bool bad = false;
-                    uint32_t p = 0;
-                    if (lv[u]) p = chunk_i8(v[u], bad);
-                    lds[lds_index(ln, u0 + u)] = p;
-                    if (bad) flags[(ln + (u0 + u) * WAVE) / CPR] = 1;
-                    any_bad |= bad;
-                }
-            }
-        } else {
-            for (int u = 0; u < CPR; ++u) {
-                const int c = ln + u * WAVE;
-                if (c < nc) {
-                    const int r = c / CPR;
-                    bool bad = false;
-                    uint32_t p = 0;
-                    if (!LIVE || live(r, c - r * CPR)) {
-                        const int4 v = ld_tile<NTL>(src + u * WAVE);
-                        p = to_i8(v.x, bad) | (to_i8(v.y, bad) << 8) | (to_i8(v.z, bad) << 16) | (to_i8(v.w, bad) << 24);
-                    }
-                    lds[r * S + (c - r * CPR)] = p;
-                    if (bad) flags[r] = 1;
-                    any_bad |= bad;
-                }
-            }
-        }
-        tile_bad = __any(any_bad);
-        wave_sync();
-        if (tile_bad) {
-            // rare (wave-uniform): chunk_i8 left arbitrary bytes in the flagged rows; their image
-            // is rebuilt with to_i8 (an out-of-domain letter -> 0x7f), so the letter counts the
-            // contract reports for them (reward, lengths) are those of the input row
-            if (ln < R && flags[ln]) {
-                const int4* row = reinterpret_cast<const int4*>(g) + (int64_t)ln * CPR;
-                for (int k = 0; k < CPR; ++k) {
-                    if (LIVE && !live(ln, k)) continue;
-                    const int4 v = row[k];
-                    bool b = false;
-                    lds[ln * S + k] = to_i8(v.x, b) | (to_i8(v.y, b) << 8) | (to_i8(v.z, b) << 16) | (to_i8(v.w, b) << 24);
-                }
-            }
-            wave_sync();
-        }
-    }
-
-    // all BLOCK threads load R rows into this tile (the block's one): consecutive threads on
-    // consecutive 16-byte chunks, every load issued before any conversion; flags as load().
-    // Block-wide barriers before and after (the expand kernels' shared parent tile: a quarter of
-    // the per-lane round trips of one wave loading all 64 rows while three wait).
-    __device__ __forceinline__ void load_block(const int32_t* __restrict__ g, int R) {
-        constexpr int U = (WAVE * CPR + BLOCK - 1) / BLOCK;
-        if (threadIdx.x < WAVE) flags[threadIdx.x] = 0;
-        __syncthreads();
-        const int nc = R * CPR;
-        const int4* src = reinterpret_cast<const int4*>(g);
-        int4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int c = (int)threadIdx.x + u * BLOCK;
-            if (c < nc) v[u] = ld_tile<NT_EXPAND_LOADS>(src + c);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int c = (int)threadIdx.x + u * BLOCK;
-            if (c >= nc) continue;
-            bool bad = false;
-            const uint32_t q = to_i8(v[u].x, bad) | (to_i8(v[u].y, bad) << 8) | (to_i8(v[u].z, bad) << 16) |
-                               (to_i8(v[u].w, bad) << 24);
-            const int r = c / CPR;
-            lds[r * S + (c - r * CPR)] = q;
-            if (bad) flags[r] = 1;
-        }
-        __syncthreads();
-    }
-
-    // the rows of the lanes in the wave-uniform mask `rows` only (a few resetting envs),
-    // cooperatively: lane l loads 16-byte chunk l % CPR of the (l / CPR)-th selected row, so a
-    // wave-instruction fetches 64 / CPR whole rows (3 at L = 36) with one round trip per group
-    __device__ __forceinline__ void load_rows(const int32_t* __restrict__ g, uint64_t rows, int R, int lane) {
-        load_rows_from([&](int r) { return g + (int64_t)r * twoL; }, rows, R, lane);
-    }
-    // rp(r): row r's source (called by every lane of the wave: it may read across lanes)
-    template <class RowPtr>
-    __device__ __forceinline__ void load_rows_from(RowPtr rp, uint64_t rows, int, int lane) {
-        constexpr int RPI = WAVE / CPR;
-        static_assert(RPI >= 1, "a row must fit one wave-instruction");
-        const int s = lane / CPR, c = lane - s * CPR;
-        const int n = __popcll(rows);
-        if ((rows >> lane) & 1ull) flags[lane] = 0;
-        wave_sync();
-        bool any_bad = false;
-        for (int k0 = 0; k0 < n; k0 += RPI) {
-            const int k = k0 + s;
-            const bool on = s < RPI && k < n;
-            uint64_t m = rows;
-            for (int i = 0; i < (on ? k : 0); ++i) m &= m - 1;
-            const int r = __builtin_ctzll(m);
-            const int32_t* row_src = rp(r);
-            if (on) {
-                const int4 v = reinterpret_cast<const int4*>(row_src)[c];
-                bool bad = false;
-                lds[r * S + c] = to_i8(v.x, bad) | (to_i8(v.y, bad) << 8) | (to_i8(v.z, bad) << 16) |
-                                 (to_i8(v.w, bad) << 24);
-                if (bad) flags[r] = 1;
-                any_bad |= bad;
-            }
-        }
-        tile_bad = tile_bad || __any(any_bad);
-        wave_sync();
-    }
-
-    // load_rows in two halves, for rows known before they are needed (an env step's truncations:
-    // step_count + 1 >= horizon before the move): fetch_rows issues the loads of the rows in the
-    // wave-uniform mask `rows` (at most RPI of them: one wave-instruction) and returns each lane's
-    // chunk; put_rows later writes the rows in `apply` (a subset) into the tile, as load_rows does
-    static constexpr bool PREFETCH_OK = true;
-    static constexpr bool LIVE_ROWS = true;  // set_lim selects the chunks a live load reads
-    static constexpr int RPI = WAVE / CPR;  // rows per wave-instruction
-    __device__ __forceinline__ int4 fetch_rows(const int32_t* __restrict__ g, uint64_t rows, int lane) const {
-        const int s = lane / CPR, c = lane - s * CPR;
-        uint64_t m = rows;
-        for (int i = 0; i < (s < RPI ? s : 0); ++i) m &= m - 1;
-        int4 v = {0, 0, 0, 0};
-        if (s < RPI && m) v = reinterpret_cast<const int4*>(g + (int64_t)__builtin_ctzll(m) * twoL)[c];
-        return v;
-    }
-    __device__ __forceinline__ void put_rows(const int4& v, uint64_t rows, uint64_t apply, int lane) {
-        const int s = lane / CPR, c = lane - s * CPR;
-        uint64_t m = rows;
-        for (int i = 0; i < (s < RPI ? s : 0); ++i) m &= m - 1;
-        if ((apply >> lane) & 1ull) flags[lane] = 0;
-        wave_sync();
-        bool bad = false;
-        if (s < RPI && m) {
-            const int r = __builtin_ctzll(m);
-            if ((apply >> r) & 1ull) {
-                lds[r * S + c] = to_i8(v.x, bad) | (to_i8(v.y, bad) << 8) | (to_i8(v.z, bad) << 16) |
-                                 (to_i8(v.w, bad) << 24);
-                if (bad) flags[r] = 1;
-            }
-        }
-        tile_bad = tile_bad || __any(bad);
-        wave_sync();
-    }
-
-    template <bool NT, bool F32, bool FULL, int UB = 0, int UE = CPR>
-    __device__ __forceinline__ void store_flat(int4* dst, int ln, int nc) const {
-#pragma unroll
-        for (int u0 = UB; u0 < UE; u0 += STAGE_UNROLL) {
-            uint32_t p[STAGE_UNROLL];
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u)
-                if (u0 + u < UE && (FULL || ln + (u0 + u) * WAVE < nc)) p[u] = lds[lds_index(ln, u0 + u)];
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u)
-                if (u0 + u < UE && (FULL || ln + (u0 + u) * WAVE < nc))
-                    out16<NT, F32>(dst + (u0 + u) * WAVE, widen4(p[u]));
-        }
-    }
-
-    // LDS -> R contiguous global rows, EXACTLY CPR store instructions on every path (a partial
-    // tile's spare lanes re-store its last chunk, same data to the same address), so the
-    // compiler's waitcnt pass can count them (rollout_kernel's one-step-ahead action load).
-    // [UB, UE): a range of the lane's chunk slots only (the rollout's split obs store)
-    static constexpr bool NT_STEP_LOADS = false;  // see ld_tile
-    template <bool NT, int UB = 0, int UE = CPR>
-    __device__ __forceinline__ void store_rows(int32_t* g, int R, int lane) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        int4* dst = reinterpret_cast<int4*>(g);
-        const int nc = R * CPR;
-        if (R == WAVE) {
-            if constexpr (NT) {  // the trajectory store with an explicit cache policy (OBS_CPOL)
-                const uint64_t b = reinterpret_cast<uint64_t>(g);
-                const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
-                const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                    reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0, WAVE * CPR * 16, 0x00020000);
-#pragma unroll
-                for (int u0 = UB; u0 < UE; u0 += STAGE_UNROLL) {
-                    uint32_t p[STAGE_UNROLL];
-#pragma unroll
-                    for (int u = 0; u < STAGE_UNROLL; ++u)
-                        if (u0 + u < UE) p[u] = lds[lds_index(ln, u0 + u)];
-#pragma unroll
-                    for (int u = 0; u < STAGE_UNROLL; ++u)
-                        if (u0 + u < UE) {
-                            const int4 v = widen4(p[u]);
-                            const v4i_t x = {v.x, v.y, v.z, v.w};
-                            __builtin_amdgcn_raw_buffer_store_b128(x, rs, (uint32_t)(ln + (u0 + u) * WAVE) * 16u, 0,
-                                                                   OBS_CPOL);
-                        }
-                }
-                return;
-            }
-            store_flat<NT, false, true, UB, UE>(dst + ln, ln, nc);
-            return;
-        }
-#pragma unroll
-        for (int u0 = UB; u0 < UE; u0 += STAGE_UNROLL) {
-            uint32_t p[STAGE_UNROLL];
-            int cc[STAGE_UNROLL];
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u) {
-                if (u0 + u >= UE) continue;
-                const int c0 = ln + (u0 + u) * WAVE;
-                const int c = c0 < nc ? c0 : nc - 1;
-                const int r = c / CPR;
-                cc[u] = c;
-                p[u] = lds[r * S + (c - r * CPR)];
-            }
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u)
-                if (u0 + u < UE) out16<NT, false>(dst + cc[u], widen4(p[u]));
-        }
-    }
-
-    // LDS -> R contiguous global rows as int8 letters (the observation_space dtype,
-    // ac_env.py:64-70): the tile's LDS image IS the int8 tile, so a 16-byte LDS read is a
-    // 16-byte global store; 2L bytes per row, (R * 2L) / 16 stores per wave (4.5 per lane at L = 36)
-    template <bool NT>
-    __device__ __forceinline__ void store_rows_i8(int8_t* g, int R, int lane) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int nd = R * CPR;  // dwords of the int8 tile
-        uint32_t* dst = reinterpret_cast<uint32_t*>(g);
-        // rows are 2L = 8m bytes: a tile starts 16-byte aligned unless m and the row index are
-        // both odd (L = 36 with an odd batch), then dword stores (wave-uniform branch)
-        const bool al = (reinterpret_cast<uintptr_t>(g) & 15u) == 0;
-        if constexpr (S == CPR) {
-            if (R == WAVE && al) {
-                // full aligned tile (wave-uniform; every step of a full batch): one 16-byte LDS
-                // read and one 16-byte store per lane and chunk, no per-dword guards (the general
-                // loop below costs ~150 VALU per wave-step at L = 36)
-                constexpr int ND = WAVE * CPR;
-#pragma unroll
-                for (int u = 0; u < (ND + 4 * WAVE - 1) / (4 * WAVE); ++u) {
-                    const int d0 = 4 * (ln + u * WAVE);
-                    if ((u + 1) * 4 * WAVE > ND && d0 >= ND) continue;  // the last, partial chunk row
-                    const v4i_t x = *reinterpret_cast<const v4i_t*>(lds + d0);
-                    if constexpr (NT) __builtin_nontemporal_store(x, reinterpret_cast<v4i_t*>(dst + d0));
-                    else *reinterpret_cast<v4i_t*>(dst + d0) = x;
-                }
-                return;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < (WAVE * CPR + 4 * WAVE - 1) / (4 * WAVE); ++u) {
-            const int d0 = 4 * (ln + u * WAVE);
-            if (d0 >= nd) continue;
-            uint32_t v[4];
-            if constexpr (S == CPR) {
-                // flat image: one 16-byte LDS read per lane, consecutive lanes consecutive
-                // 16 bytes (per-dword reads at a 16-byte lane stride were 8-way bank conflicts)
-                if (d0 + 4 <= nd) {
-                    const uint4 x = *reinterpret_cast<const uint4*>(lds + d0);
-                    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = lds[d0 + j < nd ? d0 + j : d0];
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int d = d0 + j < nd ? d0 + j : d0;
-                    const int r = d / CPR;
-                    v[j] = lds[r * S + (d - r * CPR)];
-                }
-            }
-            if (al && d0 + 4 <= nd) {
-                const v4i_t x = {(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
-                if constexpr (NT) __builtin_nontemporal_store(x, reinterpret_cast<v4i_t*>(dst + d0));
-                else *reinterpret_cast<v4i_t*>(dst + d0) = x;
-            } else {
-                for (int j = 0; j < 4 && d0 + j < nd; ++j) dst[d0 + j] = v[j];
-            }
-        }
-    }
-
-    // LDS -> global rows with row pitch `gpitch` int32; FB: flagged rows copied from their
-    // fallback row (fb_src: `fallback`, or `fallback2` for FB_RESET rows; both pitch fpitch)
-    // skip (wave-uniform): rows left unwritten (the learner's finished envs when the curriculum
-    // table surely lasts the launch: their copy writes them, step_body)
-    template <bool FB, bool NT = false, bool F32 = false>
-    __device__ __forceinline__ void store(int32_t* g, int64_t gpitch, int R, const int32_t* fallback,
-                                          int64_t fpitch, int lane, const int32_t* fallback2 = nullptr,
-                                          uint64_t skip = 0) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int nc = R * CPR;
-        if (gpitch == twoL && !(FB && tile_bad)) {
-            // contiguous rows, nothing flagged: chunk c goes to g + 4c (immediate offsets); a
-            // full tile (wave-uniform) needs no per-chunk guards
-            int4* dst = reinterpret_cast<int4*>(g) + ln;
-            if (skip) {  // the row of chunk c is c / CPR: one test against the scalar mask per chunk
-#pragma unroll
-                for (int u0 = 0; u0 < CPR; u0 += STAGE_UNROLL) {
-                    uint32_t p[STAGE_UNROLL];
-#pragma unroll
-                    for (int u = 0; u < STAGE_UNROLL; ++u)
-                        if (u0 + u < CPR && ln + (u0 + u) * WAVE < nc) p[u] = lds[lds_index(ln, u0 + u)];
-#pragma unroll
-                    for (int u = 0; u < STAGE_UNROLL; ++u) {
-                        const int c = ln + (u0 + u) * WAVE;
-                        if (u0 + u < CPR && c < nc && !((skip >> (c / CPR)) & 1ull))
-                            out16<NT, F32>(dst + (u0 + u) * WAVE, widen4(p[u]));
-                    }
-                }
-            } else if (R == WAVE) {
-                store_flat<NT, F32, true>(dst, ln, nc);
-            } else {
-                store_flat<NT, F32, false>(dst, ln, nc);
-            }
-            return;
-        }
-#pragma unroll
-        for (int u0 = 0; u0 < CPR; u0 += STAGE_UNROLL) {
-            uint32_t p[STAGE_UNROLL];
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u)
-                if (u0 + u < CPR && ln + (u0 + u) * WAVE < nc) p[u] = lds[lds_index(ln, u0 + u)];
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u) {
-                const int c = ln + (u0 + u) * WAVE;
-                if (u0 + u < CPR && c < nc && !((skip >> (c / CPR)) & 1ull)) {
-                    const int r = c / CPR;
-                    const int pos = 4 * (c - r * CPR);
-                    int4* dst = reinterpret_cast<int4*>(g + (int64_t)r * gpitch + pos);
-                    const uint32_t fc = FB ? flags[r] : 0u;
-                    if (fc) out16<false, F32>(dst, *reinterpret_cast<const int4*>(fb_src(fc, fallback, fallback2) + (int64_t)r * fpitch + pos));
-                    else out16<NT, F32>(dst, widen4(p[u]));
-                }
-            }
-        }
-    }
-
-    // ---- bit-plane registers (acx_planes.h; the env-step kernels) ----
-    static constexpr int PW = PlaneWords<NW>::value;
-
-    // lane's row -> bit planes; returns true if the row is outside the domain.  Streams the row
-    // 8 letters (two dwords) at a time through one gather per plane (pl::i8x8_to_bytes), so few
-    // values are live at once: this pack sets the env-step kernels' register peak
-    template <bool LIVE = false>  // LIVE: CodeTile only (see there)
-    __device__ __forceinline__ bool pack(int lane, PlaneRegs<PW>& p) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const uint32_t* src = lds + ln * S;
-        bool bad = flags[ln] != 0;
-#pragma unroll 1
-        for (int h = 0; h < 2; ++h) {  // one relator at a time (register peak)
-            Planes<PW> w;
-            uint64_t nz[PW];
-#pragma unroll
-            for (int j = 0; j < PW; ++j) w.s[j] = w.y[j] = nz[j] = 0ull;
-#pragma unroll
-            for (int k = 0; k < HALF; k += 2) {
-                const uint32_t d0 = src[h * HALF + k];
-                const uint32_t d1 = k + 1 < HALF ? src[h * HALF + k + 1] : 0u;
-                uint32_t s8, y8, z8;
-                pl::i8x8_to_bytes(d0, d1, s8, y8, z8);
-                const int sh = 4 * (k & 15);
-                w.s[k >> 4] |= (uint64_t)s8 << sh;
-                w.y[k >> 4] |= (uint64_t)y8 << sh;
-                nz[k >> 4] |= (uint64_t)z8 << sh;
-            }
-            int n = 0;
-#pragma unroll
-            for (int j = 0; j < PW; ++j) n += __builtin_popcountll(nz[j]);
-            const pl::Bits<PW> e = pl::bmask<PW>(n);  // zeros only as right padding <=> mask == low n bits
-#pragma unroll
-            for (int j = 0; j < PW; ++j) bad |= nz[j] != e.b[j];
-            if (h == 0) { p.w0 = w; p.n0 = n; }
-            else        { p.w1 = w; p.n1 = n; }
-        }
-        return bad;
-    }
-    __device__ __forceinline__ void unpack(int lane, const PlaneRegs<PW>& p) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        uint32_t* dst = lds + ln * S;
-        uint32_t d[CPR];
-        image(p, d);
-#pragma unroll
-        for (int k = 0; k < CPR; k += 2) *reinterpret_cast<uint2*>(dst + k) = make_uint2(d[k], d[k + 1]);
-    }
-    template <bool LIVE = false>  // LIVE: CodeTile only (see there)
-    __device__ __forceinline__ uint32_t unpack_dirty(int lane, const PlaneRegs<PW>& p) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        uint32_t* dst = lds + ln * S;
-        uint32_t d[CPR];
-        image(p, d);
-        uint32_t x0 = 0, x1 = 0;
-#pragma unroll
-        for (int k = 0; k < CPR; k += 2) {
-            const uint2 o = *reinterpret_cast<const uint2*>(dst + k);
-            if (k < HALF) x0 |= o.x ^ d[k];
-            else x1 |= o.x ^ d[k];
-            if (k + 1 < HALF) x0 |= o.y ^ d[k + 1];
-            else x1 |= o.y ^ d[k + 1];
-            *reinterpret_cast<uint2*>(dst + k) = make_uint2(d[k], d[k + 1]);
-        }
-        return (x0 != 0u ? 1u : 0u) | (x1 != 0u ? 2u : 0u);
-    }
-    __device__ __forceinline__ void unpack_half(int lane, const PlaneRegs<PW>& p, bool h1) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const Planes<PW> w = pl::psel<PW>(h1, p.w1, p.w0);
-        const int n8 = 8 * (h1 ? p.n1 : p.n0);
-        uint32_t* dst = lds + ln * S + (h1 ? HALF : 0);
-#pragma unroll
-        for (int k = 0; k < HALF; ++k) dst[k] = pl::nibbles_to_i8x4(pl::nib<PW>(w.s, k), pl::nib<PW>(w.y, k), clamp_bits(n8 - 32 * k));
-    }
-    __device__ __forceinline__ static void image(const PlaneRegs<PW>& p, uint32_t (&d)[CPR]) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const Planes<PW>& w = h ? p.w1 : p.w0;
-            const int n8 = 8 * (h ? p.n1 : p.n0);
-#pragma unroll
-            for (int k = 0; k < HALF; ++k)
-                d[h * HALF + k] = pl::nibbles_to_i8x4(pl::nib<PW>(w.s, k), pl::nib<PW>(w.y, k), clamp_bits(n8 - 32 * k));
-        }
-    }
-
-    // lane's row -> packed registers; returns true if the row is outside the domain
-    __device__ __forceinline__ bool pack(int lane, PresRegs<NW>& p) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const uint32_t* src = lds + ln * S;
-        uint32_t d[CPR];
-#pragma unroll
-        for (int k = 0; k < CPR; k += 2) {
-            const uint2 x = *reinterpret_cast<const uint2*>(src + k);
-            d[k] = x.x;
-            d[k + 1] = x.y;
-        }
-        bool bad = flags[ln] != 0;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            Word<NW> w = wzero<NW>();
-            uint64_t mlo = 0, mhi = 0;
-#pragma unroll
-            for (int k = 0; k < HALF; ++k) {
-                uint32_t c8, nz4;
-                pack4_codes(d[h * HALF + k], c8, nz4);
-                w.w[k >> 2] |= c8 << (8 * (k & 3));
-                if (k < 16) mlo |= (uint64_t)nz4 << (4 * k);
-                else mhi |= (uint64_t)nz4 << (4 * (k - 16));
-            }
-            const int n = __builtin_popcountll(mlo) + __builtin_popcountll(mhi);
-            // zeros only as right padding <=> mask == low n bits
-            const uint64_t elo = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-            const uint64_t ehi = n <= 64 ? 0ull : (n >= 128 ? ~0ull : ((1ull << (n - 64)) - 1ull));
-            bad |= (mlo != elo) || (mhi != ehi);
-            if (h == 0) { p.w0 = w; p.n0 = n; }
-            else        { p.w1 = w; p.n1 = n; }
-        }
-        return bad;
-    }
-
-    // packed registers -> lane's row
-    __device__ __forceinline__ void unpack(int lane, const PresRegs<NW>& p) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        uint32_t* dst = lds + ln * S;
-        uint32_t d[CPR];
-        image(p, d);
-#pragma unroll
-        for (int k = 0; k < CPR; k += 2) *reinterpret_cast<uint2*>(dst + k) = make_uint2(d[k], d[k + 1]);
-    }
-
-    // unpack, and return which relators differ from the row it overwrites (bit h = relator h):
-    // the int8 image is canonical (zero letters past the length), so equal relators compare equal
-    __device__ __forceinline__ uint32_t unpack_dirty(int lane, const PresRegs<NW>& p) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        uint32_t* dst = lds + ln * S;
-        uint32_t d[CPR];
-        image(p, d);
-        uint32_t x0 = 0, x1 = 0;
-#pragma unroll
-        for (int k = 0; k < CPR; k += 2) {
-            const uint2 o = *reinterpret_cast<const uint2*>(dst + k);
-            if (k < HALF) x0 |= o.x ^ d[k];
-            else x1 |= o.x ^ d[k];
-            if (k + 1 < HALF) x0 |= o.y ^ d[k + 1];
-            else x1 |= o.y ^ d[k + 1];
-            *reinterpret_cast<uint2*>(dst + k) = make_uint2(d[k], d[k + 1]);
-        }
-        return (x0 != 0u ? 1u : 0u) | (x1 != 0u ? 2u : 0u);
-    }
-
-    // relator h1 of the lane's row only: a clean move changes just its target relator, so the
-    // rollout keeps the LDS tile as the int8 image of the current states and re-images one half
-    // per step (the trajectory store then reads the whole tile)
-    __device__ __forceinline__ void unpack_half(int lane, const PresRegs<NW>& p, bool h1) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const Word<NW> w = wsel<NW>(h1, p.w1, p.w0);
-        const int n8 = 8 * (h1 ? p.n1 : p.n0);
-        uint32_t* dst = lds + ln * S + (h1 ? HALF : 0);
-#pragma unroll
-        for (int k = 0; k < HALF; ++k)
-            dst[k] = codes_to_i8x4((w.w[k >> 2] >> (8 * (k & 3))) & 0xffu, clamp_bits(n8 - 32 * k));
-    }
-
-    __device__ __forceinline__ void set_dirty(int lane, uint32_t m) const { dirty[lane] = (uint8_t)m; }
-
-    // In-place state store (g is the row block the tile was loaded from): only the 16-byte
-    // chunks of relators marked in dirty[] are written; every other chunk already holds its
-    // value in HBM (a gated move, an unchanged relator, a failed env).  Needs set_dirty for every
-    // row of the tile and a wave_sync after it.  Dirty rows flagged FB_RESET (an autoreset to an
-    // out-of-domain starting row) are copied from fallback2 (same row pitch).
-    // LIVE: a dirty relator's chunks past lim[] (the live chunks of its old and new letters, set
-    // by the caller) already hold zero padding in HBM and are not written
-    template <bool NT, bool LIVE = false>
-    __device__ __forceinline__ void store_dirty(int32_t* g, int R, int lane, const int32_t* fallback2 = nullptr) const {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int nc = R * CPR;
-        int4* dst = reinterpret_cast<int4*>(g);
-        if (tile_bad) {  // rare (wave-uniform): per-chunk fallback test
-            for (int c = ln; c < nc; c += WAVE) {
-                const int r = c / CPR;
-                const int k = c - r * CPR;
-                if (!((dirty[r] >> (k >= HALF ? 1 : 0)) & 1u)) continue;
-                if (flags[r] == FB_RESET) dst[c] = reinterpret_cast<const int4*>(fallback2)[c];
-                else if (!LIVE || live(r, k)) dst[c] = widen4(lds[r * S + k]);
-            }
-            return;
-        }
-#pragma unroll
-        for (int u0 = 0; u0 < CPR; u0 += STAGE_UNROLL) {
-            uint32_t p[STAGE_UNROLL];
-            bool wr[STAGE_UNROLL];
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u) {
-                wr[u] = false;
-                const int c = ln + (u0 + u) * WAVE;
-                if (u0 + u < CPR && c < nc) {
-                    const int r = c / CPR;
-                    const int k = c - r * CPR;
-                    wr[u] = ((dirty[r] >> (k >= HALF ? 1 : 0)) & 1u) && (!LIVE || live(r, k));
-                    if (wr[u]) p[u] = lds[r * S + k];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u) {
-                if (!wr[u]) continue;
-                out16<NT, false>(dst + ln + (u0 + u) * WAVE, widen4(p[u]));
-            }
-        }
-    }
-
-  private:
-    __device__ __forceinline__ static void image(const PresRegs<NW>& p, uint32_t (&d)[CPR]) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const Word<NW>& w = h ? p.w1 : p.w0;
-            const int n = h ? p.n1 : p.n0;
-            const int n8 = 8 * n;
-#pragma unroll
-            for (int k = 0; k < HALF; ++k)
-                d[h * HALF + k] = codes_to_i8x4((w.w[k >> 2] >> (8 * (k & 3))) & 0xffu, clamp_bits(n8 - 32 * k));
-        }
-    }
-};
 
 // CodeTile: compile-time L % 8 == 0, large L (128).  LDS holds, per 4-letter chunk, one
 // 16-bit slot = 8-bit code field | 4-bit non-zero mask << 8 (half the bytes of an int8
 // image: 8.5 KB per wave at L = 128, so LDS no longer caps occupancy); the SWAR
 // conversion happens in the cooperative load/store, and a lane's pack/unpack is plain
 // field assembly.  Row stride S dwords, S = 2 mod 4 (conflict-free 8-byte lane accesses).
+// LDS row stride (dwords) of a row of L / 2 16-bit slots: = 2 mod 4
+constexpr int code_tile_stride(int L) { return ((L / 4) % 4 == 2) ? L / 4 : L / 4 + ((6 - (L / 4) % 4) % 4); }
+
 template <int NW, int LC>
-struct CodeTile {
+struct CodeTile : PackedTileBase<LC, code_tile_stride(LC)> {
     static_assert(LC > 0 && LC % 8 == 0, "CodeTile needs a compile-time L multiple of 8");
+    using Base = PackedTileBase<LC, code_tile_stride(LC)>;
+    using Base::lds;
+    using Base::flags;
+    using Base::dirty;
+    using Base::lim;
+    using Base::live;
+    using Base::live_chunks;
     static constexpr int L = LC;
     static constexpr int twoL = 2 * LC;
     static constexpr int CPR = LC / 2;   // 4-letter chunks per row (16-bit slots)
     static constexpr int RDW = CPR / 2;  // dwords per row
-    static constexpr int S = (RDW % 4 == 2) ? RDW : RDW + ((6 - RDW % 4) % 4);
+    static constexpr int S = Base::S;
     static constexpr int HALF = CPR / 2;  // chunks per relator
     static_assert(S % 4 == 2 && RDW % 2 == 0, "row layout");
     static constexpr int LOAD_BATCH = 8;
 
-    uint32_t* lds;
-    uint8_t* flags;
-    uint8_t* dirty;  // see FastTile
-    uint8_t* lim;    // see FastTile
     uint32_t limv = 0;  // this lane's row's live chunk counts, lim0 | lim1 << 8 (set_lim)
     uint32_t dirtyv = 0;  // this lane's row's dirty bits (set_dirty)
-    bool tile_bad = false;
+    bool tile_bad = false;  // see tile_restore_flags
+    __device__ __forceinline__ void restore_flags(int lane, uint32_t code) { tile_restore_flags(flags, tile_bad, lane, code); }
+    __device__ __forceinline__ void flag_rows(int lane, uint32_t code) { tile_flag_rows(flags, tile_bad, lane, code); }
 
-    static __host__ __device__ constexpr size_t wave_bytes(int) { return (size_t)WAVE * S * 4 + 4 * WAVE; }
-    static constexpr bool PREFETCH_OK = false;  // fetch_rows / put_rows: FastTile only
-    static constexpr bool LIVE_ROWS = true;  // see FastTile
+    static constexpr bool PREFETCH_OK = false;  // fetch_rows / put_rows: stubs (see the tile interface above)
+    static constexpr bool LIVE_ROWS = true;  // set_lim selects the chunks a live load reads
     static constexpr int RPI = 1;
     __device__ __forceinline__ int4 fetch_rows(const int32_t*, uint64_t, int) const { return int4{0, 0, 0, 0}; }
     __device__ __forceinline__ void put_rows(const int4&, uint64_t, uint64_t, int) {}
     static constexpr bool NT_STEP_LOADS = true;  // see ld_tile
-    __device__ __forceinline__ void restore_flags(int lane, uint32_t code) {
-        flags[lane] = (uint8_t)code;
-        tile_bad = __any(code != 0u);
-        wave_sync();
-    }
-    __device__ __forceinline__ void flag_rows(int lane, uint32_t code) {
-        if (code) flags[lane] = (uint8_t)code;
-        tile_bad = tile_bad || __any(code != 0u);
-    }
     __device__ __forceinline__ int32_t letter(int r, int k) const {
         const uint32_t sl = slots(r)[k >> 2];
         const uint32_t d = codes_to_i8x4(sl & 0xffu, 8u * __builtin_popcount((sl >> 8) & 0xfu));
         return (int32_t)(int8_t)(d >> (8 * (k & 3)));
     }
-    __device__ __forceinline__ CodeTile(char* base, int) {
-        lds = reinterpret_cast<uint32_t*>(base);
-        flags = reinterpret_cast<uint8_t*>(base + WAVE * S * 4);
-        dirty = flags + WAVE;
-        lim = flags + 2 * WAVE;
-    }
+    __device__ __forceinline__ CodeTile(char* base, int) : Base(base) {}
     // see FastTile::set_lim / live (chunks of 4 letters; HALF chunks per relator)
     __device__ __forceinline__ void set_lim(int lane, int n0, int n1) {
         lim[2 * lane] = (uint8_t)live_chunks(n0);
@@ -983,12 +185,6 @@ struct CodeTile {
         const int l0 = lu & 0xff, l1 = (lu >> 8) & 0xff;  // scalars
         return ln < l0 || (ln >= HALF && ln < HALF + l1);  // l0 <= HALF
     }
-    __device__ __forceinline__ static int live_chunks(int n) { return n <= 0 ? 0 : n >= L ? HALF : (n + 3) >> 2; }
-    __device__ __forceinline__ bool live(int r, int k) const {
-        const int h = k >= HALF ? 1 : 0;
-        return k - h * HALF < lim[2 * r + h];
-    }
-    __device__ __forceinline__ int Lr() const { return L; }
     __device__ __forceinline__ uint16_t* slots(int r) const { return reinterpret_cast<uint16_t*>(lds + r * S); }
 
     __device__ __forceinline__ void put(int c, uint32_t slot) const {
@@ -1340,7 +536,7 @@ struct CodeTile {
         x = (x | (x << 2)) & 0x33333333u;
         return (x | (x << 1)) & 0x55555555u;
     }
-    template <bool LIVE = false>  // LIVE: CodeTile only (see there)
+    template <bool LIVE = false>  // LIVE: the tile was live-loaded (set_lim), see below
     __device__ __forceinline__ bool pack(int lane, PlaneRegs<PW>& p) const {
         static_assert(HALF % 4 == 0, "16-letter groups per relator");
         int ln = lane;
@@ -1416,7 +612,7 @@ struct CodeTile {
         put_relator(dst, p.w0, p.n0, false);
         put_relator(dst + HALF / 2, p.w1, p.n1, false);
     }
-    template <bool LIVE = false>  // LIVE: CodeTile only (see there)
+    template <bool LIVE = false>  // LIVE: the tile was live-loaded (set_lim), see below
     __device__ __forceinline__ uint32_t unpack_dirty(int lane, const PlaneRegs<PW>& p) const {
         int ln = lane;
         asm volatile("" : "+v"(ln));
@@ -1615,275 +811,6 @@ struct CodeTile {
     }
 };
 
-template <int NW, int LC, int VEC>
-struct GenericTile {
-    static constexpr bool PREFETCH_OK = false;  // fetch_rows / put_rows: FastTile only
-    static constexpr bool LIVE_ROWS = false;  // whole rows: set_lim is a no-op
-    static constexpr int RPI = 1;
-    __device__ __forceinline__ int4 fetch_rows(const int32_t*, uint64_t, int) const { return int4{0, 0, 0, 0}; }
-    __device__ __forceinline__ void put_rows(const int4&, uint64_t, uint64_t, int) {}
-    static constexpr bool NT_STEP_LOADS = false;  // see ld_tile
-    static constexpr int LMAX = LC > 0 ? LC : 16 * NW;
-    int L, twoL, rowb;
-    char* base;
-    uint8_t* flags;
-
-    static __host__ __device__ int row_bytes(int L_) {
-        const int bytes = (LC > 0) ? 2 * LC : (L_ + LMAX);
-        return (((bytes + 3) >> 2) | 1) * 4;  // odd dword stride: conflict-free per-lane reads
-    }
-    static __host__ __device__ size_t wave_bytes(int L_) { return (size_t)WAVE * row_bytes(L_) + WAVE; }
-    __device__ __forceinline__ GenericTile(char* b, int L_) {
-        L = LC > 0 ? LC : L_;
-        twoL = 2 * L;
-        rowb = row_bytes(L);
-        base = b;
-        flags = reinterpret_cast<uint8_t*>(b + WAVE * rowb);
-    }
-    __device__ __forceinline__ int Lr() const { return L; }
-    // contiguous rows
-    template <bool NT>
-    __device__ __forceinline__ void store_rows(int32_t* g, int R, int lane) const {
-        store<false, NT>(g, 2 * L, R, nullptr, 0, lane);
-    }
-    // int8 rows, byte by byte (parity instantiations)
-    template <bool NT>
-    __device__ __forceinline__ void store_rows_i8(int8_t* g, int R, int lane) const {
-        for (int i = lane; i < R * twoL; i += WAVE) g[i] = row(i / twoL)[i % twoL];
-    }
-    __device__ __forceinline__ void restore_flags(int lane, uint32_t code) {
-        flags[lane] = (uint8_t)code;
-        wave_sync();
-    }
-    __device__ __forceinline__ void flag_rows(int lane, uint32_t code) {
-        if (code) flags[lane] = (uint8_t)code;
-    }
-    __device__ __forceinline__ int32_t letter(int r, int k) const { return row(r)[k]; }
-    // the rows of the lanes in `rows` only, row by row (the generic-L instantiations serve
-    // parity, not speed)
-    __device__ __forceinline__ void load_rows(const int32_t* __restrict__ g, uint64_t rows, int R, int lane) {
-        load_rows_from([&](int r) { return g + (int64_t)r * twoL; }, rows, R, lane);
-    }
-    template <class RowPtr>
-    __device__ __forceinline__ void load_rows_from(RowPtr rp, uint64_t rows, int, int lane) {
-        if ((rows >> lane) & 1ull) flags[lane] = 0;
-        wave_sync();
-        for (uint64_t m = rows; m; m &= m - 1) {
-            const int r = __builtin_ctzll(m);
-            const int32_t* row_src = rp(r);
-            bool bad = false;
-            for (int k = lane; k < twoL; k += WAVE)
-                row(r)[k] = (int8_t)to_i8(row_src[k], bad);
-            if (__any(bad) && lane == 0) flags[r] = 1;
-        }
-        wave_sync();
-    }
-    __device__ __forceinline__ int8_t* row(int r) const { return reinterpret_cast<int8_t*>(base + r * rowb); }
-
-    // (row, pos) of a chunk of VEC int32; chunks never straddle rows (2L % VEC == 0)
-    struct It {
-        int row, pos, dq, dr, twoL;
-        __device__ __forceinline__ It(int c0, int twoL_) : twoL(twoL_) {
-            const int e0 = c0 * VEC;
-            row = e0 / twoL;
-            pos = e0 - row * twoL;
-            dq = (WAVE * VEC) / twoL;
-            dr = WAVE * VEC - dq * twoL;
-        }
-        __device__ __forceinline__ void next() {
-            pos += dr;
-            row += dq;
-            if (pos >= twoL) { pos -= twoL; ++row; }
-        }
-    };
-
-    // PIPE, LIVE: see CodeTile::load (the runtime-L path reads and writes whole rows)
-    template <bool PIPE = false, bool LIVE = false, bool NTL = false, int BATCH = 0>
-    __device__ __forceinline__ void load(const int32_t* __restrict__ g, int R, int lane) {
-        flags[lane] = 0;
-        wave_sync();
-        const int nc = (R * twoL) / VEC;
-        It it(lane, twoL);
-        for (int b0 = lane; b0 < nc; b0 += WAVE * STAGE_UNROLL) {
-            int rows[STAGE_UNROLL], poss[STAGE_UNROLL];
-            int32_t v[STAGE_UNROLL][VEC];
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u) {
-                rows[u] = it.row;
-                poss[u] = it.pos;
-                it.next();
-                if (b0 + u * WAVE < nc) {
-                    const int32_t* src = g + (int64_t)rows[u] * twoL + poss[u];
-                    if constexpr (VEC == 4) {
-                        const int4 x = *reinterpret_cast<const int4*>(src);
-                        v[u][0] = x.x; v[u][1] = x.y; v[u][2] = x.z; v[u][3] = x.w;
-                    } else {
-                        const int2 x = *reinterpret_cast<const int2*>(src);
-                        v[u][0] = x.x; v[u][1] = x.y;
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u) {
-                if (b0 + u * WAVE < nc) {
-                    bool bad = false;
-                    char* dst = base + rows[u] * rowb + poss[u];
-                    if constexpr (VEC == 4) {
-                        *reinterpret_cast<uint32_t*>(dst) = to_i8(v[u][0], bad) | (to_i8(v[u][1], bad) << 8) |
-                                                            (to_i8(v[u][2], bad) << 16) | (to_i8(v[u][3], bad) << 24);
-                    } else {
-                        *reinterpret_cast<uint16_t*>(dst) = (uint16_t)(to_i8(v[u][0], bad) | (to_i8(v[u][1], bad) << 8));
-                    }
-                    if (bad) flags[rows[u]] = 1;
-                }
-            }
-        }
-        wave_sync();
-    }
-
-    template <bool FB, bool NT = false, bool F32 = false>
-    __device__ __forceinline__ void store(int32_t* g, int64_t gpitch, int R, const int32_t* fallback,
-                                          int64_t fpitch, int lane, const int32_t* fallback2 = nullptr,
-                                          uint64_t skip = 0) const {  // skip: see FastTile::store
-        const int nc = (R * twoL) / VEC;
-        It it(lane, twoL);
-        for (int b0 = lane; b0 < nc; b0 += WAVE * STAGE_UNROLL) {
-            int rows[STAGE_UNROLL], poss[STAGE_UNROLL];
-            uint32_t p[STAGE_UNROLL];
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u) {
-                rows[u] = it.row;
-                poss[u] = it.pos;
-                it.next();
-                p[u] = 0;
-                if (b0 + u * WAVE < nc) {
-                    const char* src = base + rows[u] * rowb + poss[u];
-                    if constexpr (VEC == 4) p[u] = *reinterpret_cast<const uint32_t*>(src);
-                    else p[u] = *reinterpret_cast<const uint16_t*>(src);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < STAGE_UNROLL; ++u) {
-                if (b0 + u * WAVE >= nc || ((skip >> rows[u]) & 1ull)) continue;
-                int32_t* dst = g + (int64_t)rows[u] * gpitch + poss[u];
-                const uint32_t fc = FB ? flags[rows[u]] : 0u;
-                const bool fb = fc != 0u;
-                const int32_t* f = fb_src(fc, fallback, fallback2) + (int64_t)rows[u] * fpitch + poss[u];
-                if constexpr (VEC == 4) {
-                    out16<false, F32>(reinterpret_cast<int4*>(dst), fb ? *reinterpret_cast<const int4*>(f) : widen4(p[u]));
-                } else {
-                    int2 x;
-                    x.x = (int32_t)(int8_t)(p[u] & 0xffu);
-                    x.y = (int32_t)(int8_t)((p[u] >> 8) & 0xffu);
-                    out8<F32>(reinterpret_cast<int2*>(dst), fb ? *reinterpret_cast<const int2*>(f) : x);
-                }
-            }
-        }
-    }
-
-    // ---- bit-plane registers (acx_planes.h; the env-step kernels), letter by letter ----
-    static constexpr int PW = PlaneWords<NW>::value;
-    __device__ __forceinline__ void pack_relator(const int8_t* src, Planes<PW>& w, int& n, bool& bad) const {
-#pragma unroll
-        for (int j = 0; j < PW; ++j) w.s[j] = w.y[j] = 0ull;
-        n = 0;
-        bool zero_seen = false;
-#pragma unroll
-        for (int k = 0; k < LMAX; ++k) {
-            int b = src[k];
-            if (LC == 0) b = (k < L) ? b : 0;
-            const bool nz = b != 0;
-            w.s[k >> 6] |= (uint64_t)(nz && b < 0) << (k & 63);
-            w.y[k >> 6] |= (uint64_t)(nz && (b & 1) == 0) << (k & 63);
-            n += nz;
-            bad |= nz && zero_seen;
-            zero_seen |= !nz;
-        }
-    }
-    template <bool LIVE = false>  // LIVE: CodeTile only (see there)
-    __device__ __forceinline__ bool pack(int lane, PlaneRegs<PW>& p) const {
-        const int8_t* r = row(lane);
-        bool bad = flags[lane] != 0;
-        pack_relator(r, p.w0, p.n0, bad);
-        pack_relator(r + L, p.w1, p.n1, bad);
-        return bad;
-    }
-    __device__ __forceinline__ void unpack_relator(int8_t* dst, const Planes<PW>& w, int n) const {
-#pragma unroll
-        for (int k = 0; k < LMAX; ++k) {
-            const uint32_t code = (uint32_t)(((w.y[k >> 6] >> (k & 63)) & 1ull) << 1 | ((w.s[k >> 6] >> (k & 63)) & 1ull));
-            const uint32_t letter = (0xFE02FF01u >> (code << 3)) & 0xffu;  // code -> 1, -1, 2, -2
-            if (LC > 0 || k < L) dst[k] = (int8_t)(k < n ? letter : 0u);
-        }
-    }
-    __device__ __forceinline__ void unpack(int lane, const PlaneRegs<PW>& p) const {
-        int8_t* r = row(lane);
-        unpack_relator(r, p.w0, p.n0);
-        unpack_relator(r + L, p.w1, p.n1);
-    }
-    __device__ __forceinline__ void unpack_half(int lane, const PlaneRegs<PW>& p, bool h1) const {
-        unpack_relator(row(lane) + (h1 ? L : 0), pl::psel<PW>(h1, p.w1, p.w0), h1 ? p.n1 : p.n0);
-    }
-    template <bool LIVE = false>  // LIVE: CodeTile only (see there)
-    __device__ __forceinline__ uint32_t unpack_dirty(int lane, const PlaneRegs<PW>& p) const {
-        unpack(lane, p);
-        return 3u;
-    }
-
-    __device__ __forceinline__ void pack_relator(const int8_t* src, Word<NW>& w, int& n, bool& bad) const {
-        w = wzero<NW>();
-        n = 0;
-        bool zero_seen = false;
-#pragma unroll
-        for (int k = 0; k < LMAX; ++k) {
-            int b = src[k];
-            if (LC == 0) b = (k < L) ? b : 0;
-            const bool nz = b != 0;
-            const uint32_t code = nz ? ((((uint32_t)~b & 1u) << 1) | (((uint32_t)b >> 7) & 1u)) : 0u;
-            w.w[k >> 4] |= code << (2 * (k & 15));
-            n += nz;
-            bad |= nz && zero_seen;
-            zero_seen |= !nz;
-        }
-    }
-    __device__ __forceinline__ bool pack(int lane, PresRegs<NW>& p) const {
-        const int8_t* r = row(lane);
-        bool bad = flags[lane] != 0;
-        pack_relator(r, p.w0, p.n0, bad);
-        pack_relator(r + L, p.w1, p.n1, bad);
-        return bad;
-    }
-    __device__ __forceinline__ void unpack_relator(int8_t* dst, const Word<NW>& w, int n) const {
-#pragma unroll
-        for (int k = 0; k < LMAX; ++k) {
-            const uint32_t code = (w.w[k >> 4] >> (2 * (k & 15))) & 3u;
-            const uint32_t letter = (0xFE02FF01u >> (code << 3)) & 0xffu;  // code -> 1, -1, 2, -2
-            if (LC > 0 || k < L) dst[k] = (int8_t)(k < n ? letter : 0u);
-        }
-    }
-    __device__ __forceinline__ void unpack(int lane, const PresRegs<NW>& p) const {
-        int8_t* r = row(lane);
-        unpack_relator(r, p.w0, p.n0);
-        unpack_relator(r + L, p.w1, p.n1);
-    }
-    // relator h1 of the lane's row only (the rollout's clean moves change one relator)
-    __device__ __forceinline__ void unpack_half(int lane, const PresRegs<NW>& p, bool h1) const {
-        unpack_relator(row(lane) + (h1 ? L : 0), wsel<NW>(h1, p.w1, p.w0), h1 ? p.n1 : p.n0);
-    }
-    // runtime-L tiles (parity tests at any L) track no dirty relators: every row is written
-    __device__ __forceinline__ uint32_t unpack_dirty(int lane, const PresRegs<NW>& p) const {
-        unpack(lane, p);
-        return 3u;
-    }
-    __device__ __forceinline__ void set_dirty(int, uint32_t) const {}
-    __device__ __forceinline__ void set_lim(int, int, int) const {}  // whole rows (see FastTile)
-    __device__ __forceinline__ void widen_lim(int, int, int) const {}
-    template <bool NT, bool LIVE = false>
-    __device__ __forceinline__ void store_dirty(int32_t* g, int R, int lane, const int32_t* fallback2 = nullptr) const {
-        store<true, NT>(g, twoL, R, g, twoL, lane, fallback2);
-    }
-};
-
 // The int8 trajectory rows of a tile with flagged rows (rare, wave-uniform branch): byte by byte,
 // flagged rows as the int8 values of their fallback row (numpy's astype(int8) wrap)
 template <class Tile>
@@ -1957,59 +884,6 @@ __device__ __forceinline__ bool wave_ctx(int64_t rows, WaveCtx& w) {
 // ---------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------
-struct StepArgs {
-    const int32_t* state_in;
-    int32_t* state_out;
-    const int32_t* action;
-    const int32_t* reset_state;
-    int32_t* step_count;
-    int32_t* reward;
-    uint8_t* done;
-    uint8_t* truncated;
-    int32_t* lengths_out;
-    int32_t* final_obs;
-    uint8_t* err;
-    int32_t* err_count;
-    // learner-side outputs (acx_step_learner; all NULL for acx_step)
-    const int64_t* action64;
-    float* obs_f32;
-    float* reward_f32;
-    float* done_f32;
-    uint8_t* action_hist;
-    int32_t* episode_len;
-    int64_t B;
-    int L, horizon, cyclical, hist_cap;
-    // acx_learner_step: the round-1 curriculum fused into the step (training.py:319-352).
-    // cur_ws NULL: none.  cur_ws (uint64 words): [0] launch sequence number, [1, 2] reserved,
-    // then the tiles' counts, the groups' totals and arrival words (cur_publish, cur_prefix)
-    uint64_t* cur_ws;
-    const int32_t* cur_states;  // (n_states, 2L) initial states
-    int64_t n_states;
-    int32_t* cur_next;          // [1] max(states_processed) + 1
-    int32_t* curr_index;        // (B)
-    uint8_t* needs_host;        // (B)
-    // state_out == state_in (set by the launcher): the state store writes changed relators only
-    int in_place;
-    // next-step autoreset (acx_step_next; NULL: same-step): per env, its episode ended on the
-    // previous call -- this call resets it instead of stepping, and records whether it ends now
-    uint8_t* pending;
-    // lengths-carrying step (acx_step_lengths): lengths_out holds the rows' relator lengths on
-    // entry (canonical rows), so only their letters are read and written
-    int live;
-    // move-history ring (NULL: move k of an episode at row k): per env, the row of its current
-    // episode's move 0; an episode's first move sets it to hist_t mod hist_cap (hist_t: the
-    // caller's step counter), so envs whose episodes are out of phase still write this step's
-    // moves to one row -- coalesced -- instead of one cache line per lane
-    int32_t* hist_base;
-    int64_t hist_t;
-    // tests only (acx_internal_learner_ranking_fails): ranking waits give up at once, as one that
-    // polled 2^20 times would (1: every wait, needs_host = 3; 2: only the last tile's total)
-    int cur_fail;
-    // acx_step_lengths_reduced (live steps only; NULL: none): per env, bit 0 = both relators are
-    // non-empty and freely reduced, bit 1 = and cyclically reduced, as the previous step left them.
-    // A conjugation of such a row reads only its target relator (step_body).  Written every call.
-    uint8_t* reduced;
-};
 
 // ---------------------------------------------------------------------------------
 // The curriculum's ranking inside the step kernel (acx_learner_step, one launch).  Finished envs
@@ -2035,14 +909,12 @@ struct StepArgs {
 //     earlier tile never scheduled) gives up and flags its finished envs needs_host = 3
 //     (CurriculumRecord.process raises), so the launch always ends.  Any give-up -- a tile's
 //     prefix, or the last tile's total, after which next_index is stale -- also sets the sticky
-//     word [2]: every later launch then ranks nothing (its finished envs get needs_host = 3) until
+//     failure word: every later launch then ranks nothing (its finished envs get needs_host = 3) until
 //     the host re-zeroes the workspace (LearnerEnv.reset_workspace, which also restores
 //     next_index from curr_index), since a give-up can leave a group's arrival word incomplete;
 //     CurriculumRecord.process raises on the word.  Concurrent launches on one workspace are not
 //     supported (they would overwrite each other's words; nothing detects it).
-// cur_ws (uint64 words): [0] sequence number, [1] base, [2] sticky failure word, [3, 3 + T) tile
-// counts, [3 + T, 3 + T + G) group totals, [3 + T + G, 3 + T + 2G) group arrival words (T tiles,
-// G groups).
+// The words of cur_ws are laid out by acx_cur_layout.h (CurLayout below).
 // ---------------------------------------------------------------------------------
 constexpr uint64_t CUR_SET = 1ull << 62;
 constexpr uint32_t CUR_FAIL = 0xffffffffu;
@@ -2061,22 +933,19 @@ __device__ __forceinline__ void cur_store(uint64_t* p, uint64_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// uint64 words between two groups' arrival words, the launch's only same-address atomics (64
-// tiles add to each): 256 bytes apart, one per channel-interleave unit, the step is 6 % faster
-// than with the words packed (fresh episodes 0.1257 vs 0.1345 ms, steady state 0.159 vs 0.165,
-// profiles/r05/r05x_learner_probe_stride.json; spacing the tile count words too changed nothing).
-// acx_curriculum_workspace (acx_curriculum.hip) sizes the workspace with the same value
-#define ACX_CUR_ARRIVE_STRIDE 32
+// the words of a.cur_ws (acx_cur_layout.h: the one definition, which acx_curriculum_workspace
+// sizes the workspace with); a tile is a wave's envs, a group's tiles are polled a lane each
+static_assert(cur_layout::TILE_ENVS == WAVE && cur_layout::GROUP_TILES == WAVE, "one tile per wave, one tile per lane");
 struct CurLayout {
     int64_t tiles, groups;
     uint64_t *base, *tile, *group, *arrive;
     __device__ __forceinline__ CurLayout(const StepArgs& a) {
-        tiles = (a.B + WAVE - 1) / WAVE;
-        groups = (tiles + WAVE - 1) / WAVE;
-        base = a.cur_ws + 1;
-        tile = a.cur_ws + 3;
-        group = tile + tiles;
-        arrive = group + groups;
+        tiles = cur_layout::tiles(a.B);
+        groups = cur_layout::groups(tiles);
+        base = a.cur_ws + cur_layout::BASE;
+        tile = a.cur_ws + cur_layout::TILES;
+        group = a.cur_ws + cur_layout::group_totals(tiles);
+        arrive = a.cur_ws + cur_layout::arrivals(tiles);
     }
 };
 
@@ -2097,11 +966,11 @@ __device__ __forceinline__ uint64_t cur_publish(const StepArgs& a, const WaveCtx
     uint64_t word = cur_word(seq, cnt);
     asm volatile("" : "+v"(word) : "s"((uint32_t)cnext));
     cur_store(c.tile + t, word);
-    return __hip_atomic_fetch_add(c.arrive + g * ACX_CUR_ARRIVE_STRIDE, (1ull << 32) | cnt, __ATOMIC_RELAXED,
+    return __hip_atomic_fetch_add(c.arrive + g * cur_layout::ARRIVE_STRIDE, (1ull << 32) | cnt, __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_AGENT);
 }
-// the sticky failure word (cur_ws[2], see above)
-__device__ __forceinline__ void cur_set_failed(const StepArgs& a) { cur_store(a.cur_ws + 2, 1ull); }
+// the sticky failure word (see above)
+__device__ __forceinline__ void cur_set_failed(const StepArgs& a) { cur_store(a.cur_ws + cur_layout::FAILED, 1ull); }
 
 // the add that completed its group publishes the group's total and clears the arrival word for
 // the next launch
@@ -2113,7 +982,7 @@ __device__ __forceinline__ void cur_publish_end(const StepArgs& a, const WaveCtx
     const int64_t gsize = (c.tiles - g * WAVE) < WAVE ? (c.tiles - g * WAVE) : WAVE;
     if ((int64_t)(old >> 32) + 1 == gsize) {
         cur_store(c.group + g, cur_word(seq, (uint32_t)old + cnt));
-        cur_store(c.arrive + g * ACX_CUR_ARRIVE_STRIDE, 0ull);
+        cur_store(c.arrive + g * cur_layout::ARRIVE_STRIDE, 0ull);
     }
 }
 
@@ -2217,7 +1086,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a) {
     const bool cur = LEARN && a.cur_ws != nullptr;  // kernel argument: uniform
     if (!wave_ctx(a.B, w)) return;
     // the launch's sequence number, read before this tile publishes (cur_publish)
-    const uint32_t cseq = cur ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)cur_load(a.cur_ws)) : 0u;
+    const uint32_t cseq = cur ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)cur_load(a.cur_ws + cur_layout::SEQ)) : 0u;
     // next_index as this launch found it (the last tile replaces it only after every tile has
     // published, i.e. read it).  exhausted (round 1 complete): no finished env gets a state from
     // the table, so no tile waits for its ranking; the host draws for every finished env.
@@ -2230,7 +1099,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a) {
     const bool exhausted = cur && cnext >= a.n_states;
     // a give-up in an earlier launch (cur_set_failed) left the workspace unusable until the host
     // re-zeroes it: this launch ranks nothing
-    const bool broken = cur && __builtin_amdgcn_readfirstlane((int)(uint32_t)cur_load(a.cur_ws + 2)) != 0;
+    const bool broken = cur && __builtin_amdgcn_readfirstlane((int)(uint32_t)cur_load(a.cur_ws + cur_layout::FAILED)) != 0;
     // the table surely lasts the launch (every finished env gets an initial state from it): a
     // finished env is not autoreset here -- its rows are left out of the tile's stores and written
     // once, by the curriculum copy, which then needs no drain of the tile's stores (below)
@@ -2515,7 +1384,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a) {
                 // next_index stale: the workspace is marked failed (the host restores both)
                 if (tot != CUR_FAIL) {
                     *a.cur_next = (int32_t)((int64_t)tot < a.n_states ? (int64_t)tot : a.n_states);
-                    cur_store(a.cur_ws, (uint64_t)((cseq + 1u) & CUR_SEQ_MASK));
+                    cur_store(a.cur_ws + cur_layout::SEQ, (uint64_t)((cseq + 1u) & CUR_SEQ_MASK));
                 } else {
                     cur_set_failed(a);
                 }
@@ -2924,23 +1793,6 @@ __global__ __launch_bounds__(BLOCK, LC == 128 ? 4 : Occupancy<LC>::waves_per_sim
     step_body<NW, LC, VEC, false, true>(a);
 }
 
-struct RolloutArgs {
-    int32_t* state;
-    const int32_t* actions;
-    const uint32_t* packed;  // or: move ids pre-packed by pack_actions_kernel (actions unused)
-    const int32_t* reset_state;
-    int32_t* step_count;
-    int32_t* obs_traj;
-    int32_t* reward_traj;
-    uint8_t* done_traj;
-    uint8_t* trunc_traj;
-    uint8_t* err;
-    int32_t* err_count;
-    int64_t B;
-    int T, L, horizon, cyclical;
-    int8_t* obs_traj8;  // acx_rollout_obs8: the trajectory as int8 letters (obs_traj unused)
-};
-
 // OBS: 0 no trajectory, 1 int32 obs trajectory (obs_traj), 2 int8 obs trajectory (obs_traj8)
 template <int NW, int LC, int VEC, int OBS>
 __global__ __launch_bounds__(BLOCK, Occupancy<LC>::waves_per_simd) void rollout_kernel(RolloutArgs a) {
@@ -3187,17 +2039,6 @@ struct ExpandLaunchSmem {
         const size_t k = (size_t)WAVE * KEY_GROUP * (size_t)((4 * L + 16 + 63) / 64) * 8;
         return ((t > k ? t : k) + 15) & ~(size_t)15;
     }
-};
-
-struct ExpandArgs {
-    const int32_t* parents;
-    int32_t* children;
-    int32_t* child_len;
-    uint64_t* child_key;
-    uint8_t* err;
-    int32_t* err_count;
-    int64_t N;
-    int L, cyclical, kw64;
 };
 
 template <int NW, int LC, int VEC>
@@ -3598,16 +2439,6 @@ __global__ __launch_bounds__(BLOCK) void expand12_rows_kernel(ExpandArgs a) {
     if (nerr && a.err_count) atomicAdd(a.err_count, nerr);
 }
 
-struct CanonArgs {
-    const int32_t* state_in;
-    int32_t* state_out;
-    int32_t* lengths_out;
-    uint8_t* err;
-    int32_t* err_count;
-    int64_t B;
-    int L, cyclical;
-};
-
 // simplify_presentation (utils.py:246-283): assert valid, then reduce both relators
 template <int NW, int LC, int VEC>
 __global__ __launch_bounds__(BLOCK) void canon_kernel(CanonArgs a) {
@@ -3641,14 +2472,6 @@ __global__ __launch_bounds__(BLOCK) void canon_kernel(CanonArgs a) {
     tile.template store<true, NT_STATE>(a.state_out + w.r0 * twoL, twoL, w.R, a.state_in + w.r0 * twoL, twoL,
                                                  w.lane);
 }
-
-struct UnpackArgs {
-    const uint64_t* keys;
-    int32_t* states;
-    int32_t* lengths_out;
-    int64_t M;
-    int L, kw64;
-};
 
 template <int NW, int LC, int VEC>
 __global__ __launch_bounds__(BLOCK) void unpack_keys_kernel(UnpackArgs a) {
@@ -3890,6 +2713,99 @@ struct UnpackLaunch {
 #ifndef ACX_PART  // the C-ABI lives in the main object only
 using namespace acx;
 
+// ---- the step entries' argument checks (a failed check is ACX_E_ARG; B == 0 is ACX_OK once the
+// ---- ranges hold, before any pointer is looked at) ----
+static bool dims_ok(int64_t B, int32_t L) { return B >= 0 && L >= 1 && L <= ACX_MAX_L; }
+// a required buffer of rows: present and 16-byte aligned
+static bool rows16(const void* p) { return p && aligned16(p); }
+static bool hist_range_ok(int32_t hist_cap, int64_t hist_t) { return hist_cap >= 0 && hist_t >= 0; }
+
+// The three plain step kinds (ACX_STEP_PLAN_*: acx_step, acx_step_lengths, acx_step_lengths_reduced):
+// checks the kind's arguments and fills `a` with all of them but the move ids.  Called by the entry
+// itself and by acx_step_plan_create, so a plan is checked exactly as its entry.  The lengths kinds
+// are in place (state_out == state_in) and need lengths; reduced is _LENGTHS_REDUCED's alone.
+static int plain_step_args(StepArgs& a, int32_t kind, const int32_t* state_in, int32_t* state_out,
+                           const int32_t* reset_state, int32_t* step_count, int32_t* reward, uint8_t* done,
+                           uint8_t* truncated, int32_t* lengths, uint8_t* reduced, int32_t* final_obs, uint8_t* err,
+                           int32_t* err_count, int64_t B, int32_t L, int32_t horizon, int32_t cyclical) {
+    const bool live = kind != ACX_STEP_PLAN_STEP, with_reduced = kind == ACX_STEP_PLAN_LENGTHS_REDUCED;
+    if (!dims_ok(B, L) || (!with_reduced && reduced)) return ACX_E_ARG;
+    if (B > 0) {
+        if (!rows16(state_in) || !rows16(state_out)) return ACX_E_ARG;
+        if (reset_state && !step_count) return ACX_E_ARG;
+        if (live && (state_out != state_in || !lengths)) return ACX_E_ARG;
+        if (with_reduced && !reduced) return ACX_E_ARG;
+    }
+    a.state_in = state_in;
+    a.state_out = state_out;
+    a.reset_state = reset_state;
+    a.step_count = step_count;
+    a.reward = reward;
+    a.done = done;
+    a.truncated = truncated;
+    a.lengths_out = lengths;
+    a.final_obs = final_obs;
+    a.err = err;
+    a.err_count = err_count;
+    a.B = B;
+    a.L = L;
+    a.horizon = horizon;
+    a.cyclical = cyclical;
+    a.live = live ? 1 : 0;
+    a.reduced = reduced;
+    return ACX_OK;
+}
+
+// a plain step from checked arguments and this call's move ids
+static int launch_plain_step(StepArgs a, const int32_t* action, void* stream) {
+    if (a.B == 0) return ACX_OK;
+    if (!action) return ACX_E_ARG;
+    a.action = action;
+    StepLaunch f{a, (hipStream_t)stream, false};
+    return dispatch(a.L, f);
+}
+
+// the move history of the entries that record one (checked by the entry)
+static void set_history(StepArgs& a, uint8_t* action_hist, int32_t hist_cap, int32_t* hist_base, int64_t hist_t,
+                        int32_t* episode_len) {
+    a.action_hist = action_hist;
+    a.hist_cap = hist_cap;
+    a.hist_base = hist_base;
+    a.hist_t = hist_t;
+    a.episode_len = episode_len;
+}
+
+// acx_step_learner and acx_learner_step: the arguments they share, checked and filled (in place)
+static int learner_step_args(StepArgs& a, int32_t* state, const int32_t* action, const int64_t* action_i64,
+                             const int32_t* reset_state, int32_t* step_count, float* obs_f32, float* reward_f32,
+                             float* done_f32, uint8_t* done, uint8_t* truncated, uint8_t* action_hist,
+                             int32_t hist_cap, int32_t* hist_base, int64_t hist_t, int32_t* episode_len, uint8_t* err,
+                             int32_t* err_count, int64_t B, int32_t L, int32_t horizon, int32_t cyclical) {
+    if (!dims_ok(B, L) || !hist_range_ok(hist_cap, hist_t) || (hist_base && !action_hist)) return ACX_E_ARG;
+    if (B == 0) return ACX_OK;
+    if (!rows16(state) || !step_count || (!action == !action_i64) || (action_hist && hist_cap == 0)) return ACX_E_ARG;
+    if (obs_f32 && !aligned16(obs_f32)) return ACX_E_ARG;
+    a.state_in = state;
+    a.state_out = state;
+    a.action = action;
+    a.reset_state = reset_state;
+    a.step_count = step_count;
+    a.done = done;
+    a.truncated = truncated;
+    a.err = err;
+    a.err_count = err_count;
+    a.action64 = action_i64;
+    a.obs_f32 = obs_f32;
+    a.reward_f32 = reward_f32;
+    a.done_f32 = done_f32;
+    a.B = B;
+    a.L = L;
+    a.horizon = horizon;
+    a.cyclical = cyclical;
+    set_history(a, action_hist, hist_cap, hist_base, hist_t, episode_len);
+    return ACX_OK;
+}
+
 extern "C" {
 
 int32_t acx_key_words(int32_t L) { return (4 * L + 16 + 63) / 64; }
@@ -3904,70 +2820,37 @@ int acx_step(const int32_t* state_in, int32_t* state_out, const int32_t* action,
              int32_t* step_count, int32_t* reward, uint8_t* done, uint8_t* truncated, int32_t* lengths_out,
              int32_t* final_obs, uint8_t* err, int32_t* err_count, int64_t B, int32_t L, int32_t horizon,
              int32_t cyclical, void* stream) {
-    if (B < 0 || L < 1 || L > ACX_MAX_L) return ACX_E_ARG;
-    if (B == 0) return ACX_OK;
-    if (!state_in || !state_out || !action) return ACX_E_ARG;
-    if (!aligned16(state_in) || !aligned16(state_out)) return ACX_E_ARG;
-    if (reset_state && !step_count) return ACX_E_ARG;
-    StepArgs a{state_in, state_out, action, reset_state, step_count, reward, done, truncated,
-               lengths_out, final_obs, err, err_count, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-               B, L, horizon, cyclical, 0};
-    StepLaunch f{a, (hipStream_t)stream, false};
-    return dispatch(L, f);
+    StepArgs a{};
+    const int rc = plain_step_args(a, ACX_STEP_PLAN_STEP, state_in, state_out, reset_state, step_count, reward, done,
+                                   truncated, lengths_out, nullptr, final_obs, err, err_count, B, L, horizon, cyclical);
+    return rc != ACX_OK ? rc : launch_plain_step(a, action, stream);
 }
 
 int acx_step_lengths(int32_t* state, const int32_t* action, const int32_t* reset_state, int32_t* step_count,
                      int32_t* reward, uint8_t* done, uint8_t* truncated, int32_t* lengths, int32_t* final_obs,
                      uint8_t* err, int32_t* err_count, int64_t B, int32_t L, int32_t horizon, int32_t cyclical,
                      void* stream) {
-    if (B < 0 || L < 1 || L > ACX_MAX_L) return ACX_E_ARG;
-    if (B == 0) return ACX_OK;
-    if (!state || !action || !lengths) return ACX_E_ARG;
-    if (!aligned16(state)) return ACX_E_ARG;
-    if (reset_state && !step_count) return ACX_E_ARG;
-    StepArgs a{state, state, action, reset_state, step_count, reward, done, truncated, lengths, final_obs, err,
-               err_count, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, L, horizon, cyclical, 0};
-    a.live = 1;
-    StepLaunch f{a, (hipStream_t)stream, false};
-    return dispatch(L, f);
+    StepArgs a{};
+    const int rc = plain_step_args(a, ACX_STEP_PLAN_LENGTHS, state, state, reset_state, step_count, reward, done,
+                                   truncated, lengths, nullptr, final_obs, err, err_count, B, L, horizon, cyclical);
+    return rc != ACX_OK ? rc : launch_plain_step(a, action, stream);
 }
 
 int acx_step_lengths_reduced(int32_t* state, const int32_t* action, const int32_t* reset_state, int32_t* step_count,
                              int32_t* reward, uint8_t* done, uint8_t* truncated, int32_t* lengths, uint8_t* reduced,
                              int32_t* final_obs, uint8_t* err, int32_t* err_count, int64_t B, int32_t L,
                              int32_t horizon, int32_t cyclical, void* stream) {
-    if (B < 0 || L < 1 || L > ACX_MAX_L) return ACX_E_ARG;
-    if (B == 0) return ACX_OK;
-    if (!state || !action || !lengths || !reduced) return ACX_E_ARG;
-    if (!aligned16(state)) return ACX_E_ARG;
-    if (reset_state && !step_count) return ACX_E_ARG;
-    StepArgs a{state, state, action, reset_state, step_count, reward, done, truncated, lengths, final_obs, err,
-               err_count, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, L, horizon, cyclical, 0};
-    a.live = 1;
-    a.reduced = reduced;
-    StepLaunch f{a, (hipStream_t)stream, false};
-    return dispatch(L, f);
+    StepArgs a{};
+    const int rc = plain_step_args(a, ACX_STEP_PLAN_LENGTHS_REDUCED, state, state, reset_state, step_count, reward, done,
+                                   truncated, lengths, reduced, final_obs, err, err_count, B, L, horizon, cyclical);
+    return rc != ACX_OK ? rc : launch_plain_step(a, action, stream);
 }
 
 // a per-call step with everything but the move ids resolved once (acx.h): the launch is then a
 // three-argument call -- at 65,536 envs a caller's ctypes call with 17 arguments took as long as
 // half the kernel, and the host, not the GPU, set the eager rate
 struct acx_step_plan {
-    int32_t kind;
-    const int32_t* state_in;
-    int32_t* state_out;
-    const int32_t* reset_state;
-    int32_t* step_count;
-    int32_t* reward;
-    uint8_t* done;
-    uint8_t* truncated;
-    int32_t* lengths;
-    uint8_t* reduced;
-    int32_t* final_obs;
-    uint8_t* err;
-    int32_t* err_count;
-    int64_t B;
-    int32_t L, horizon, cyclical;
+    StepArgs a;  // checked and filled by plain_step_args; action is the launch's
 };
 
 acx_step_plan* acx_step_plan_create(int32_t kind, const int32_t* state_in, int32_t* state_out,
@@ -3975,36 +2858,17 @@ acx_step_plan* acx_step_plan_create(int32_t kind, const int32_t* state_in, int32
                                     uint8_t* truncated, int32_t* lengths, uint8_t* reduced, int32_t* final_obs,
                                     uint8_t* err, int32_t* err_count, int64_t B, int32_t L, int32_t horizon,
                                     int32_t cyclical) {
-    // the checks of the entry the plan calls (acx_step / acx_step_lengths / _reduced), made once
+    // the checks of the kind's entry (acx_step / acx_step_lengths / _reduced), made once
     if (kind < ACX_STEP_PLAN_STEP || kind > ACX_STEP_PLAN_LENGTHS_REDUCED) return nullptr;
-    if (B < 0 || L < 1 || L > ACX_MAX_L) return nullptr;
-    if (B > 0) {
-        if (!state_in || !state_out || !aligned16(state_in) || !aligned16(state_out)) return nullptr;
-        if (reset_state && !step_count) return nullptr;
-        if (kind != ACX_STEP_PLAN_STEP && (state_out != state_in || !lengths)) return nullptr;
-        if (kind == ACX_STEP_PLAN_LENGTHS_REDUCED && !reduced) return nullptr;
-    }
-    if (kind != ACX_STEP_PLAN_LENGTHS_REDUCED && reduced) return nullptr;
-    return new (std::nothrow) acx_step_plan{kind, state_in, state_out, reset_state, step_count, reward, done, truncated,
-                                            lengths, reduced, final_obs, err, err_count, B, L, horizon, cyclical};
+    StepArgs a{};
+    if (plain_step_args(a, kind, state_in, state_out, reset_state, step_count, reward, done, truncated, lengths, reduced,
+                        final_obs, err, err_count, B, L, horizon, cyclical) != ACX_OK)
+        return nullptr;
+    return new (std::nothrow) acx_step_plan{a};
 }
 
 int acx_step_plan_launch(const acx_step_plan* p, const int32_t* action, void* stream) {
-    if (!p) return ACX_E_ARG;
-    switch (p->kind) {
-    case ACX_STEP_PLAN_STEP:
-        return acx_step(p->state_in, p->state_out, action, p->reset_state, p->step_count, p->reward, p->done,
-                        p->truncated, p->lengths, p->final_obs, p->err, p->err_count, p->B, p->L, p->horizon,
-                        p->cyclical, stream);
-    case ACX_STEP_PLAN_LENGTHS:
-        return acx_step_lengths(p->state_out, action, p->reset_state, p->step_count, p->reward, p->done, p->truncated,
-                                p->lengths, p->final_obs, p->err, p->err_count, p->B, p->L, p->horizon, p->cyclical,
-                                stream);
-    default:
-        return acx_step_lengths_reduced(p->state_out, action, p->reset_state, p->step_count, p->reward, p->done,
-                                        p->truncated, p->lengths, p->reduced, p->final_obs, p->err, p->err_count,
-                                        p->B, p->L, p->horizon, p->cyclical, stream);
-    }
+    return p ? launch_plain_step(p->a, action, stream) : ACX_E_ARG;
 }
 
 void acx_step_plan_destroy(acx_step_plan* p) { delete p; }
@@ -4014,17 +2878,17 @@ int acx_step_next(const int32_t* state_in, int32_t* state_out, const int32_t* ac
                   uint8_t* pending, uint8_t* action_hist, int32_t hist_cap, int32_t* hist_base, int64_t hist_t,
                   int32_t* episode_len, uint8_t* err, int32_t* err_count, int64_t B, int32_t L, int32_t horizon,
                   int32_t cyclical, void* stream) {
-    if (B < 0 || L < 1 || L > ACX_MAX_L || hist_cap < 0 || hist_t < 0 || (hist_base && !action_hist)) return ACX_E_ARG;
-    if (B == 0) return ACX_OK;
-    if (!state_in || !state_out || !action || !reset_state || !step_count || !pending) return ACX_E_ARG;
+    if (!hist_range_ok(hist_cap, hist_t) || (hist_base && !action_hist)) return ACX_E_ARG;
+    // acx_step's arguments (no final_obs), then this entry's own
+    StepArgs a{};
+    const int rc = plain_step_args(a, ACX_STEP_PLAN_STEP, state_in, state_out, reset_state, step_count, reward, done,
+                                   truncated, lengths_out, nullptr, nullptr, err, err_count, B, L, horizon, cyclical);
+    if (rc != ACX_OK || B == 0) return rc;
+    if (!action || !reset_state || !step_count || !pending) return ACX_E_ARG;
     if ((action_hist != nullptr) != (hist_cap > 0) || (episode_len && !action_hist)) return ACX_E_ARG;
-    if (!aligned16(state_in) || !aligned16(state_out)) return ACX_E_ARG;
-    StepArgs a{state_in, state_out, action, reset_state, step_count, reward, done, truncated, lengths_out, nullptr,
-               err, err_count, nullptr, nullptr, nullptr, nullptr, action_hist, episode_len, B, L, horizon, cyclical,
-               hist_cap};
+    a.action = action;
     a.pending = pending;
-    a.hist_base = hist_base;
-    a.hist_t = hist_t;
+    set_history(a, action_hist, hist_cap, hist_base, hist_t, episode_len);
     // with a move history: the learner instantiation (it compiles the history writes)
     StepLaunch f{a, (hipStream_t)stream, action_hist != nullptr};
     return dispatch(L, f);
@@ -4035,15 +2899,12 @@ int acx_step_learner(int32_t* state, const int32_t* action, const int64_t* actio
                      uint8_t* truncated, uint8_t* action_hist, int32_t hist_cap, int32_t* hist_base, int64_t hist_t,
                      int32_t* episode_len, int32_t* final_obs, uint8_t* err, int32_t* err_count, int64_t B, int32_t L,
                      int32_t horizon, int32_t cyclical, void* stream) {
-    if (B < 0 || L < 1 || L > ACX_MAX_L || hist_cap < 0 || hist_t < 0 || (hist_base && !action_hist)) return ACX_E_ARG;
-    if (B == 0) return ACX_OK;
-    if (!state || !step_count || (!action == !action_i64) || (action_hist && hist_cap == 0)) return ACX_E_ARG;
-    if (!aligned16(state) || (obs_f32 && !aligned16(obs_f32))) return ACX_E_ARG;
-    StepArgs a{state, state, action, reset_state, step_count, nullptr, done, truncated, nullptr, final_obs, err,
-               err_count, action_i64, obs_f32, reward_f32, done_f32, action_hist, episode_len, B, L, horizon,
-               cyclical, hist_cap};
-    a.hist_base = hist_base;
-    a.hist_t = hist_t;
+    StepArgs a{};
+    const int rc = learner_step_args(a, state, action, action_i64, reset_state, step_count, obs_f32, reward_f32, done_f32,
+                                     done, truncated, action_hist, hist_cap, hist_base, hist_t, episode_len, err,
+                                     err_count, B, L, horizon, cyclical);
+    if (rc != ACX_OK || B == 0) return rc;
+    a.final_obs = final_obs;
     StepLaunch f{a, (hipStream_t)stream, true};
     return dispatch(L, f);
 }
@@ -4053,16 +2914,15 @@ int acx_step_record(const int32_t* state_in, int32_t* state_out, const int32_t* 
                     int32_t* final_obs, uint8_t* action_hist, int32_t hist_cap, int32_t* hist_base, int64_t hist_t,
                     int32_t* episode_len, uint8_t* err, int32_t* err_count, int64_t B, int32_t L, int32_t horizon,
                     int32_t cyclical, void* stream) {
-    if (B < 0 || L < 1 || L > ACX_MAX_L || hist_cap < 0 || hist_t < 0) return ACX_E_ARG;
-    if (B == 0) return ACX_OK;
-    if (!state_in || !state_out || !action || !step_count || !action_hist || hist_cap == 0) return ACX_E_ARG;
-    if (!aligned16(state_in) || !aligned16(state_out)) return ACX_E_ARG;
-    // the learner instantiation (it compiles the history writes) with the plain step's outputs
-    StepArgs a{state_in, state_out, action, reset_state, step_count, reward, done, truncated, lengths_out, final_obs,
-               err, err_count, nullptr, nullptr, nullptr, nullptr, action_hist, episode_len, B, L, horizon, cyclical,
-               hist_cap};
-    a.hist_base = hist_base;
-    a.hist_t = hist_t;
+    if (!hist_range_ok(hist_cap, hist_t)) return ACX_E_ARG;
+    // the learner instantiation (it compiles the history writes) with the plain step's arguments
+    StepArgs a{};
+    const int rc = plain_step_args(a, ACX_STEP_PLAN_STEP, state_in, state_out, reset_state, step_count, reward, done,
+                                   truncated, lengths_out, nullptr, final_obs, err, err_count, B, L, horizon, cyclical);
+    if (rc != ACX_OK || B == 0) return rc;
+    if (!action || !step_count || !action_hist || hist_cap == 0) return ACX_E_ARG;
+    a.action = action;
+    set_history(a, action_hist, hist_cap, hist_base, hist_t, episode_len);
     StepLaunch f{a, (hipStream_t)stream, true};
     return dispatch(L, f);
 }
@@ -4070,7 +2930,10 @@ int acx_step_record(const int32_t* state_in, int32_t* state_out, const int32_t* 
 // acx_curriculum.hip: where acx_learner_step's part of the shared workspace starts (int32 words)
 int64_t acx_internal_curriculum_fused_offset(int64_t B);
 
-int64_t acx_learner_failure_word(int64_t B) { return acx_internal_curriculum_fused_offset(B) + 4; }  // cur_ws[2]
+// int32 words into the workspace: the fused part's uint64 word cur_layout::FAILED
+int64_t acx_learner_failure_word(int64_t B) {
+    return acx_internal_curriculum_fused_offset(B) + 2 * cur_layout::FAILED;
+}
 
 static int g_learner_fail = 0;  // tests only
 // tests only: acx_learner_step's ranking polls give up at once: 1 every one, 2 only the last tile's
@@ -4083,26 +2946,27 @@ int acx_learner_step(int32_t* state, const int32_t* action, const int64_t* actio
                      int32_t* episode_len, uint8_t* err, int32_t* err_count, const int32_t* curriculum_states,
                      int64_t n_states, int32_t* next_index, int32_t* curr_index, uint8_t* needs_host,
                      int32_t* workspace, int64_t B, int32_t L, int32_t horizon, int32_t cyclical, void* stream) {
-    if (B < 0 || L < 1 || L > ACX_MAX_L || hist_cap < 0 || n_states < 0 || n_states > INT32_MAX) return ACX_E_ARG;
-    if (hist_t < 0 || (hist_base && !action_hist)) return ACX_E_ARG;
+    if (n_states < 0 || n_states > INT32_MAX) return ACX_E_ARG;
     if (B >= (1ll << 31)) return ACX_E_ARG;  // the look-back's 32-bit prefixes (next_index + finished envs)
-    if (B == 0) return ACX_OK;
-    if (!state || !step_count || (!action == !action_i64) || (action_hist && hist_cap == 0)) return ACX_E_ARG;
+    StepArgs a{};
+    const int rc = learner_step_args(a, state, action, action_i64, reset_state, step_count, obs_f32, reward_f32, done_f32,
+                                     done, truncated, action_hist, hist_cap, hist_base, hist_t, episode_len, err,
+                                     err_count, B, L, horizon, cyclical);
+    if (rc != ACX_OK || B == 0) return rc;
     if (!done || !truncated || !reset_state || !curriculum_states || !next_index || !curr_index || !needs_host ||
         !workspace)
         return ACX_E_ARG;
-    if (!aligned16(state) || (obs_f32 && !aligned16(obs_f32))) return ACX_E_ARG;
     if ((L % 2) == 0 && (!aligned16(reset_state) || !aligned16(curriculum_states))) return ACX_E_ARG;  // int4 row copies
     // one launch: the step kernel ranks the finished envs itself (cur_publish / cur_prefix) in its part of the
     // workspace (acx_curriculum_workspace(B) int32 words, zeroed before the first call, 8-byte aligned)
     int32_t* ws = workspace + acx_internal_curriculum_fused_offset(B);
     if ((reinterpret_cast<uintptr_t>(ws) & 7u) != 0) return ACX_E_ARG;
-    StepArgs a{state, state, action, reset_state, step_count, nullptr, done, truncated, nullptr, nullptr, err,
-               err_count, action_i64, obs_f32, reward_f32, done_f32, action_hist, episode_len, B, L, horizon,
-               cyclical, hist_cap, reinterpret_cast<uint64_t*>(ws), curriculum_states, n_states, next_index,
-               curr_index, needs_host};
-    a.hist_base = hist_base;
-    a.hist_t = hist_t;
+    a.cur_ws = reinterpret_cast<uint64_t*>(ws);
+    a.cur_states = curriculum_states;
+    a.n_states = n_states;
+    a.cur_next = next_index;
+    a.curr_index = curr_index;
+    a.needs_host = needs_host;
     a.cur_fail = g_learner_fail;
     StepLaunch f{a, (hipStream_t)stream, true};
     return dispatch(L, f);

@@ -520,7 +520,7 @@ __device__ __forceinline__ uint32_t spread4(uint32_t n4) { return __umul24(n4, 0
 
 // sign / y nibbles of 4 letters -> their int8 image, the first `s` bits (s = 8m, m = 0..4 letters)
 // kept and the rest zero: each byte's 2-bit code selects the letter {1,-1,2,-2} from v_perm's
-// first source, a byte past m selects zero from the second (acx_kernels.hip codes_to_i8x4)
+// first source, a byte past m selects zero from the second (acx_tile_io.h codes_to_i8x4)
 __device__ __forceinline__ uint32_t nibbles_to_i8x4(uint32_t s4, uint32_t y4, uint32_t s) {
     const uint32_t sel = spread4(s4) | (spread4(y4) << 1) | (uint32_t)(0x04040404ull << s);
     return __builtin_amdgcn_perm(0u, 0xFE02FF01u, sel);

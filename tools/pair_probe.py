@@ -43,7 +43,7 @@ def patched_source():
     ins("    const int64_t env = r0 + er;\n", f"    uint64_t PT_[{NST}] = {{}};\n    PT_[0] = {stamp};\n", before=False)
     ins("        if (__any(badm != 0u)) {", f"        PT_[1] = {stamp};\n")
     ins("    // the env's move: on a clean env", f"    PT_[2] = {stamp};\n")
-    ins("    // this lane's relator re-imaged (a failed env keeps its loaded image)", f"    PT_[3] = {stamp};\n")
+    ins("    // this lane's relator changed (a failed env keeps its row)", f"    PT_[3] = {stamp};\n")
     ins("    // the state store.  Relator masks", f"    PT_[4] = {stamp};\n")
     end = (f"{{ PT_[5] = {stamp}; __builtin_amdgcn_s_waitcnt(0); PT_[6] = {stamp}; "
            "if (lane == 0 && a.final_obs) { uint64_t* P_ = reinterpret_cast<uint64_t*>(a.final_obs) + "
