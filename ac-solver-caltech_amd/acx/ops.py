@@ -69,7 +69,7 @@ LIVE_TILE_L = (36, 128)
 LENGTHS_STEP_L = (128,)
 # acx_step at a compile-time L = 36 tile with B <= this many envs runs the small-batch kernel
 # (step_pair_kernel: two lanes per env, one per relator, so config 2's 65,536 envs are two waves
-# per SIMD instead of one); csrc acx_kernels.hip SMALL_STEP_MAX_B
+# per SIMD instead of one); csrc acx_step_pair.h SMALL_STEP_MAX_B
 SMALL_STEP_MAX_B = 2 * 4 * 256 * 64
 
 

@@ -21,8 +21,9 @@ OUT = os.path.join(HERE, "acx", "libacx.so")
 INCLUDE = os.path.join(REPO, "include")
 SOURCES = ["acx_kernels.hip", "acx_bfs.hip", "acx_sbfs.hip", "acx_features.hip", "acx_curriculum.hip", "acx_words.hip",
            "acx_greedy.hip", "acx_search.cpp"]
-# acx_kernels.hip is also compiled once per instantiation part (-DACX_PART=n, see the file's
-# "extern template" block), in parallel: the runtime-L generic sets took ~7 minutes in one object
+# acx_kernels.hip is also compiled once per instantiation part (-DACX_PART=n, see the part table
+# and its "extern template" block in acx_launch.h), in parallel: the runtime-L generic sets took
+# ~7 minutes in one object
 KERNEL_PARTS = 10
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ACX_OFFLOAD_ARCH", "gfx950")

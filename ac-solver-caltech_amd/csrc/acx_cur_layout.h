@@ -1,6 +1,6 @@
 // acx_cur_layout.h -- the layout of acx_learner_step's part of the curriculum workspace, in uint64
 // words from its start (acx_internal_curriculum_fused_offset(B) int32 words into the caller's
-// buffer).  The one definition: the step kernel's ranking (acx_kernels.hip, CurLayout) addresses
+// buffer).  The one definition: the step kernel's ranking (acx_cur_rank.h, CurLayout) addresses
 // the words with it, and acx_curriculum_workspace / acx_learner_failure_word size and locate them
 // with it.
 //   [SEQ] launch sequence number, [BASE] the scan's base, [FAILED] sticky failure word,

@@ -204,7 +204,7 @@ int acx_curriculum_assign(const uint8_t* done, const uint8_t* truncated, const i
 }
 
 // acx_learner_step (acx_kernels.hip) ranks the finished envs inside its step kernel with a
-// look-back over per-64-env-tile status words (acx_kernels.hip: cur_publish / cur_prefix); its
+// look-back over per-64-env-tile status words (acx_cur_rank.h: cur_publish / cur_prefix); its
 // part of the workspace (acx_cur_layout.h) starts after this file's (next_index copy + per-block
 // counts), so either call may use one workspace.
 int64_t acx_internal_curriculum_fused_offset(int64_t B) {

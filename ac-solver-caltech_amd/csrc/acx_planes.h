@@ -1,5 +1,5 @@
 // acx_planes.h -- the per-lane Andrews-Curtis word algebra on bit planes, for the env-step
-// kernels (acx_kernels.hip: step_kernel, rollout_kernel).
+// kernels (acx_step_kernel.h, acx_step_pair.h, acx_rollout_kernel.h).
 //
 // A relator of up to 64*PW letters is two bit planes of PW uint64 words each (letter k at bit
 // k): s = "the letter is an inverse" (x^-1, y^-1), y = "the letter is y^{+-1}".  The letter's
@@ -410,7 +410,7 @@ ACX_HD __forceinline__ int ac_move_clean(Planes<PW>& w0, int& n0, Planes<PW>& w1
     return ACX_ERR_NONE;
 }
 
-// ac_move_clean split over the two lanes of an env (acx_kernels.hip step_pair_kernel, one lane per
+// ac_move_clean split over the two lanes of an env (acx_step_pair.h step_pair_kernel, one lane per
 // relator, PW = 1).  The lane holds relator h (w, n) and its reversal rw = prev(w, n); from its
 // partner it has the other relator (pw, pn) and that one's reversal (prw).  On the lane of the
 // move's target relator (ac_moves.py:167-179: i = (id + 1) & 1) it returns ac_move_clean's

@@ -1,6 +1,6 @@
-// acx_step_args.h -- the argument structs of the env-side kernels (acx_kernels.hip: step, rollout,
-// expand12, canonicalize, unpack).  They are passed by value as kernel arguments: field order and
-// types fix the offsets the compiled kernels read.
+// acx_step_args.h -- the argument structs of the env-side kernels (step, rollout, expand12,
+// canonicalize, unpack: acx_kernels.hip's header comment maps their headers).  They are passed by
+// value as kernel arguments: field order and types fix the offsets the compiled kernels read.
 #pragma once
 #include <stdint.h>
 

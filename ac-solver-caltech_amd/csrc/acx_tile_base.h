@@ -1,6 +1,6 @@
 // acx_tile_base.h -- what FastTile and CodeTile have in common: a wave's LDS slice (the row image,
 // then per-row flag, dirty and live-chunk bytes) and the members that only touch those bytes.
-// A plain base struct; each tile adds its own row image format on top (acx_kernels.hip states the
+// A plain base struct; each tile adds its own row image format on top (acx_tile.h states the
 // interface as a whole).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // acx_tile_fast.h -- FastTile: the LDS tile for a compile-time L with L % 4 == 0 below 64 (L = 36).
-// The interface the three tiles share is stated in acx_kernels.hip.
+// The interface the three tiles share is stated in acx_tile.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -446,7 +446,7 @@ struct FastTile : PackedTileBase<LC, fast_tile_stride(LC)> {
     // lane's row -> bit planes; returns true if the row is outside the domain.  Streams the row
     // 8 letters (two dwords) at a time through one gather per plane (pl::i8x8_to_bytes), so few
     // values are live at once: this pack sets the env-step kernels' register peak
-    template <bool LIVE = false>  // LIVE: ignored (see the tile interface, acx_kernels.hip)
+    template <bool LIVE = false>  // LIVE: ignored (see the tile interface, acx_tile.h)
     __device__ __forceinline__ bool pack(int lane, PlaneRegs<PW>& p) const {
         int ln = lane;
         asm volatile("" : "+v"(ln));
@@ -489,7 +489,7 @@ struct FastTile : PackedTileBase<LC, fast_tile_stride(LC)> {
 #pragma unroll
         for (int k = 0; k < CPR; k += 2) *reinterpret_cast<uint2*>(dst + k) = make_uint2(d[k], d[k + 1]);
     }
-    template <bool LIVE = false>  // LIVE: ignored (see the tile interface, acx_kernels.hip)
+    template <bool LIVE = false>  // LIVE: ignored (see the tile interface, acx_tile.h)
     __device__ __forceinline__ uint32_t unpack_dirty(int lane, const PlaneRegs<PW>& p) const {
         int ln = lane;
         asm volatile("" : "+v"(ln));

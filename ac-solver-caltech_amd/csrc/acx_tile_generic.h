@@ -1,5 +1,5 @@
 // acx_tile_generic.h -- GenericTile: the LDS tile for a runtime L (parity at any L <= 128), letter
-// by letter.  The interface the three tiles share is stated in acx_kernels.hip.
+// by letter.  The interface the three tiles share is stated in acx_tile.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,7 +11,7 @@ namespace acx {
 
 template <int NW, int LC, int VEC>
 struct GenericTile {
-    static constexpr bool PREFETCH_OK = false;  // fetch_rows / put_rows: stubs (see the tile interface, acx_kernels.hip)
+    static constexpr bool PREFETCH_OK = false;  // fetch_rows / put_rows: stubs (see the tile interface, acx_tile.h)
     static constexpr bool LIVE_ROWS = false;  // whole rows: set_lim is a no-op
     static constexpr int RPI = 1;
     __device__ __forceinline__ int4 fetch_rows(const int32_t*, uint64_t, int) const { return int4{0, 0, 0, 0}; }
@@ -194,7 +194,7 @@ struct GenericTile {
             zero_seen |= !nz;
         }
     }
-    template <bool LIVE = false>  // LIVE: ignored (see the tile interface, acx_kernels.hip)
+    template <bool LIVE = false>  // LIVE: ignored (see the tile interface, acx_tile.h)
     __device__ __forceinline__ bool pack(int lane, PlaneRegs<PW>& p) const {
         const int8_t* r = row(lane);
         bool bad = flags[lane] != 0;
@@ -218,7 +218,7 @@ struct GenericTile {
     __device__ __forceinline__ void unpack_half(int lane, const PlaneRegs<PW>& p, bool h1) const {
         unpack_relator(row(lane) + (h1 ? L : 0), pl::psel<PW>(h1, p.w1, p.w0), h1 ? p.n1 : p.n0);
     }
-    template <bool LIVE = false>  // LIVE: ignored (see the tile interface, acx_kernels.hip)
+    template <bool LIVE = false>  // LIVE: ignored (see the tile interface, acx_tile.h)
     __device__ __forceinline__ uint32_t unpack_dirty(int lane, const PlaneRegs<PW>& p) const {
         unpack(lane, p);
         return 3u;
@@ -270,7 +270,7 @@ struct GenericTile {
         return 3u;
     }
     __device__ __forceinline__ void set_dirty(int, uint32_t) const {}
-    __device__ __forceinline__ void set_lim(int, int, int) const {}  // whole rows: stubs (see the tile interface, acx_kernels.hip)
+    __device__ __forceinline__ void set_lim(int, int, int) const {}  // whole rows: stubs (see the tile interface, acx_tile.h)
     __device__ __forceinline__ void widen_lim(int, int, int) const {}
     template <bool NT, bool LIVE = false>
     __device__ __forceinline__ void store_dirty(int32_t* g, int R, int lane, const int32_t* fallback2 = nullptr) const {

@@ -1,8 +1,8 @@
 // acx_tile_io.h -- what moves a tile of rows between HBM and LDS: the wave-level barrier, the
 // int32 <-> int8 letter and 2-bit code conversions, the 16-byte load / store helpers with their
 // cache-policy constants, and the fallback-row codes of rows outside the packed domain.  Used by
-// the tile classes (acx_tile_fast.h, acx_tile_generic.h, CodeTile in acx_kernels.hip) and by the
-// kernels.
+// the tile classes (acx_tile_code.h, acx_tile_fast.h, acx_tile_generic.h; their interface is in
+// acx_tile.h) and by the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -211,6 +211,62 @@ def test_expand12_vs_oracle(L, cyc):
     assert np.array_equal(res["lengths"].cpu().numpy()[ok], lens[ok])
 
 
+def _key_length_bytes(keys, L):
+    """bits [4L, 4L + 16) of packed keys (.., KW) uint64: the two length bytes"""
+    lo, sh = (4 * L) // 64, (4 * L) % 64
+    v = keys[..., lo] >> np.uint64(sh)
+    if sh > 48:
+        v = v | (keys[..., lo + 1] << np.uint64(64 - sh))
+    return v & np.uint64(0xFFFF)
+
+
+@pytest.mark.parametrize("L", [7, 36, 110, 128])
+@pytest.mark.parametrize("cyc", [0, 1])
+def test_expand12_keys_only_equals_keys_of_children(L, cyc):
+    """The keys-only call (the searches' path) against the call with children and against the
+    oracle, errored children's sentinel included.  N = 133 is two full tiles and a partial one; the
+    four L reach all four expand12 kernels and all three tiles: keys-only is expand12_keys_kernel
+    at L = 7 (GenericTile) and 36 (FastTile) and expand12_kernel's staged key groups at 128
+    (CodeTile); with children it is the children kernel at 7, the rows kernel at 36 and 128, and
+    expand12_kernel at 110.  Six planted parents (x y x y .. and its inverse) each have exactly two
+    children whose move empties a relator (err 1)."""
+    import acx
+    rng = np.random.default_rng(1000 + L + cyc)
+    N = 133
+    s = np.zeros((N, 2 * L), np.int32)
+    for b in range(N):
+        for h in range(2):
+            n = int(rng.integers(1, L + 1))
+            s[b, h * L : h * L + n] = rng.choice([1, -1, 2, -2], size=n)
+    xy = np.tile(np.array([1, 2], np.int32), L)[:L]
+    for row, n in zip((3, 63, 64, 100, 127, 132), (1, 2, L // 2, L - 1, L, 3)):
+        s[row] = 0
+        s[row, :n] = xy[:n]
+        s[row, L : L + n] = -xy[:n][::-1]
+    ch, lens, err = O.expand12(s, L, cyc)
+    bad = err != 0
+    ok = ~bad
+    assert bad.sum() >= 12 and bad.mean() <= 0.05  # not vacuous: errored children, and few of them
+
+    par = torch.as_tensor(s).to(DEV)
+    both = acx.ops.expand12(par, cyclical=bool(cyc), children=True, keys=True)
+    konly = acx.ops.expand12(par, cyclical=bool(cyc), children=False, keys=True, lengths=True, err=True)
+    assert "children" not in konly
+    for res in (both, konly):
+        assert np.array_equal(res["err"].cpu().numpy(), err)
+        assert np.array_equal(res["lengths"].cpu().numpy()[ok], lens[ok])
+    assert np.array_equal(both["children"].cpu().numpy(), ch)
+    k_both = both["keys"].cpu().numpy().view(np.uint64)
+    k_only = konly["keys"].cpu().numpy().view(np.uint64)
+    assert np.array_equal(k_both[ok], k_only[ok])
+    # an errored child's key: both length bytes 0xFF (acx.h)
+    assert (_key_length_bytes(k_both, L)[bad] == 0xFFFF).all()
+    assert (_key_length_bytes(k_only, L)[bad] == 0xFFFF).all()
+    okt = torch.as_tensor(ok).to(DEV)
+    back = acx.ops.unpack_keys(konly["keys"][okt], L)
+    assert torch.equal(back, both["children"][okt])
+
+
 @pytest.mark.parametrize("L,N", [(36, 64 * 5 + 17), (128, 64 * 3 + 1), (17, 333), (36, 64)])
 def test_expand12_children_with_bad_parents(L, N):
     """Block-per-tile children kernel: children, lengths and error codes of every (parent,

@@ -1,6 +1,7 @@
 #!/bin/bash
-# Build L = 36-only (or, with ONLY=L128, L = 128-only) variants of the env-step kernels (acx_kernels.hip with its
-# headers + acx_curriculum.hip, C-ABI included) for in-process A/B timing (tools/ab_rollout.py), in parallel:
+# Build L = 36-only (or, with ONLY=L128, L = 128-only) variants of the env-step kernels (acx_kernels.hip: the C-ABI,
+# with the kernels and launchers in the headers it includes, + acx_curriculum.hip) for in-process A/B timing
+# (tools/ab_rollout.py), in parallel.  -DFLAGs reach every header (ACX_ISA_*_ONLY is read by dispatch, acx_launch.h):
 #   bash tools/ab_build.sh NAME "-DFLAG=.. -DFLAG2=.." [NAME2 "FLAGS2" ...]   -> abv/libacx_NAME.so (OUT=dir: another
 # directory under the repo, e.g. one that travels with gpurun; abv/ does not)
 # Another revision: SRC=/path/to/checkout/ac-solver-caltech_amd/csrc/acx_kernels.hip bash tools/ab_build.sh NAME ""

@@ -3,7 +3,10 @@
     python tools/kernel_resources.py [object.o] [name-substring ...]
 
 Reads the .hip_fatbin section of an object built by ac-solver-caltech_amd/build.py (no GPU,
-no rebuild), unbundles the gfx950 code object and prints its kernel metadata notes.
+no rebuild), unbundles the gfx950 code object and prints its kernel metadata notes.  The default
+object is the main one of csrc/acx_kernels.hip (the L = 36 instantiations of the kernels in
+acx_step_kernel.h, acx_step_pair.h, acx_rollout_kernel.h and acx_expand_kernels.h); the other
+instantiations are in acx_kernels.hip.p1.o .. p10.o (the part table in acx_launch.h).
 """
 import os
 import re

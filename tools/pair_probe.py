@@ -1,10 +1,12 @@
 """Where config 2's step launch spends its time: step_pair_kernel with per-wave timestamps.
 
-Builds (here, no GPU: --build) a variant of ac-solver-caltech_amd/csrc/acx_kernels.hip whose
-step_pair_kernel stamps s_memrealtime (the 100 MHz device clock, one time base for the chip) at
-its phases and writes them per wave to a buffer passed in acx_step's final_obs argument (the
+Builds (here, no GPU: --build) a variant of the env-side kernels (ac-solver-caltech_amd/csrc/
+acx_kernels.hip, the one translation unit) whose step_pair_kernel (acx_step_pair.h) stamps
+s_memrealtime (the 100 MHz device clock, one time base for the chip) at its phases and writes them
+per wave to a buffer passed in acx_step's final_obs argument (the
 variant's final_obs write is patched out); the product source is not changed (the stamps are
-patched into a copy at text anchors).  On the GPU
+patched at text anchors into a copy of acx_step_pair.h, which stands in a scratch copy of csrc/ so
+that every quoted include resolves as in the product).  On the GPU
 box it walks config 2 (65,536 envs, L = 36, Miller-Schupp starts, uniform moves, in place, the
 bench's step_api walk) and records a few launches:
 
@@ -18,12 +20,14 @@ import argparse
 import ctypes
 import json
 import os
+import shutil
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-SRC = os.path.join(REPO, "ac-solver-caltech_amd", "csrc", "acx_kernels.hip")
+CSRC = os.path.join(REPO, "ac-solver-caltech_amd", "csrc")
+SRC = os.path.join(CSRC, "acx_step_pair.h")  # holds step_pair_kernel
 OUT = os.path.join(REPO, "ab6", "libacx_probe.so")
 NST = 8  # stamps per wave (7 used)
 
@@ -59,14 +63,15 @@ def patched_source():
 
 def build():
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    tmp = os.path.join(REPO, "ab6", "acx_kernels_probe.hip")
-    with open(tmp, "w") as f:
+    tmp = os.path.join(REPO, "ab6", "probe_src")  # csrc/ with the patched header in the original's place
+    shutil.rmtree(tmp, ignore_errors=True)
+    shutil.copytree(CSRC, tmp)
+    with open(os.path.join(tmp, os.path.basename(SRC)), "w") as f:
         f.write(patched_source())
-    csrc = os.path.dirname(SRC)
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                           "-Wno-pass-failed", "-DACX_ISA_L36_ONLY", "-I" + os.path.join(REPO, "include"), "-I" + csrc,
-                           tmp, os.path.join(csrc, "acx_curriculum.hip"), "-o", OUT])
-    os.remove(tmp)
+                           "-Wno-pass-failed", "-DACX_ISA_L36_ONLY", "-I" + os.path.join(REPO, "include"),
+                           os.path.join(tmp, "acx_kernels.hip"), os.path.join(tmp, "acx_curriculum.hip"), "-o", OUT])
+    shutil.rmtree(tmp)
     print(OUT)
 
 
