@@ -17,7 +17,11 @@ DEV = torch.device("cuda:0")
 
 def _starts(L, B):
     from bench import ms_starts
-    st = ms_starts(L, B)
+    if L >= 18:
+        st = ms_starts(L, B)
+    else:  # the same presentations, each relator cut to its first L letters
+        wide = ms_starts(18, B)
+        st = np.concatenate([wide[:, :L], wide[:, 18:18 + L]], 1)
     triv = np.zeros((8, 2 * L), np.int32)
     for r, (a0, a1) in enumerate([(1, 2), (1, -2), (-1, 2), (-1, -2), (2, 1), (2, -1), (-2, 1), (-2, -1)]):
         triv[r, 0], triv[r, L] = a0, a1
@@ -25,11 +29,15 @@ def _starts(L, B):
     return st
 
 
-@pytest.mark.parametrize("L,record", [(36, False), (36, True), (128, False), (18, True)])
+@pytest.mark.parametrize("L,record", [(36, False), (36, True), (128, False), (18, True)] +
+                         [(L, record) for L in (16, 33, 49, 65) for record in (False, True)])
 def test_next_step_autoreset_matches_oracle_model(L, record):
+    """L = 16, 33, 49, 65: acx_step_next / acx_step_record on the generic tiles -- a full tile and the
+    first L of the NW = 3, 4 and 8 classes (1000 envs: at 3000 the presentations cut to 16 letters
+    hold a pair whose move empties a relator, which this model does not cover)."""
     from acx.envs.ac_env import VecACEnv
     from oracle import oracle as O
-    B, H, T = 3000, 7, 30
+    B, H, T = (3000 if L in (18, 36, 128) else 1000), 7, 30
     starts = _starts(L, B)
     env = VecACEnv(starts, horizon_length=H, device=DEV, record_actions=record, info_format="actions",
                    autoreset_mode="next_step")

@@ -233,6 +233,72 @@ def test_vec_env_lengths_after_rollout_and_direct_writes(L):
     assert _lib.E_ARG < 0
 
 
+@pytest.mark.parametrize("L", [36, 128])
+@pytest.mark.parametrize("cyc", [True, False])
+def test_vec_env_handover_on_the_reduced_kernel(L, cyc, monkeypatch):
+    """The env-level handover with VecACEnv.step on acx_step_lengths_reduced, the kernel that trusts
+    the carried flags, at a batch where ops.lengths_step_for would not pick it at L = 36 (patched to
+    True): a rollout invalidates lengths and flags (the next step is acx_step, which rewrites the
+    lengths; the one after zeroes the flags and is back on the reduced kernel), reset_env zeroes one
+    row's flag while the others stay trusted, and a direct write into env.state with _lengths_ok =
+    _reduced_ok = False (as LearnerEnv hands rows over).  The rows written are unreduced, so a stale
+    flag would leave a conjugation's other relator unsimplified.  Every step equals a twin stepped
+    with acx_step."""
+    from acx import VecACEnv, ops
+    monkeypatch.setattr(ops, "lengths_step_for", lambda B, L: True)
+    B, H, T = 64 * 5 + 3, 8, 6
+    rng = np.random.default_rng(30 + L + cyc)
+    start = _rows(L, B, rng)
+    env = VecACEnv(start, horizon_length=H, device=DEV, cyclical=cyc)
+    twin = VecACEnv(start, horizon_length=H, device=DEV, cyclical=cyc)
+    assert env._live_tile
+    acts = rng.integers(0, 12, size=(T + 12, B)).astype(np.int32)
+    unreduced = np.zeros((24, 2 * L), np.int32)
+    unreduced[:, :6] = (1, -1, 2, 2, -1, 1)  # r0 = y y, r1 = x y once reduced
+    unreduced[:, L:L + 4] = (2, -2, 1, 2)
+    n_flagged = 0
+
+    def both_step(t, want_live):
+        nonlocal n_flagged
+        live = env._lengths_ok  # what VecACEnv.step is about to choose
+        assert live == want_live, t
+        o1, r1, d1, t1, i1 = env.step(_t(acts[t]))
+        assert env._lengths_ok and env._reduced_ok == want_live, t
+        twin._lengths_ok = False  # the twin always takes acx_step (it rewrites its lengths each call)
+        o2, r2, d2, t2, i2 = twin.step(_t(acts[t]))
+        for x, y in ((o1, o2), (r1, r2), (d1, d2), (t1, t2), (env.step_count, twin.step_count), (env.err, twin.err),
+                     (env.lengths, twin.lengths)):
+            assert torch.equal(x, y), t
+        m = (d1 | t1).bool()
+        assert torch.equal(i1["final_observation"][m], i2["final_observation"][m]), t
+        if want_live:
+            n_flagged += _check_reduced_flags(env.reduced, env.state, L, t)
+
+    for t in range(3):  # on the reduced kernel from the start: the flags fill
+        both_step(t, True)
+    env.rollout(_t(acts[3:3 + T]))
+    assert not env._lengths_ok and not env._reduced_ok
+    for t in range(3, 3 + T):
+        twin._lengths_ok = False
+        twin.step(_t(acts[t]))
+    assert torch.equal(env.state, twin.state) and torch.equal(env.step_count, twin.step_count)
+    both_step(3 + T, False)  # acx_step: lengths rewritten, flags still unknown
+    both_step(4 + T, True)   # flags zeroed, then trusted again
+    both_step(5 + T, True)
+    for e in (env, twin):  # one row replaced while the other rows' flags stay trusted
+        e.reset_env(7, unreduced[0])
+    assert int(env.reduced[7]) == 0 and env._reduced_ok
+    both_step(6 + T, True)
+    both_step(7 + T, True)
+    for e in (env, twin):  # a learner's direct write
+        e.state[40:64].copy_(_t(unreduced))
+        e._lengths_ok = e._reduced_ok = False
+    both_step(8 + T, False)
+    for t in range(9 + T, 12 + T):
+        both_step(t, True)
+    assert n_flagged > B  # the flags were in use: most rows stepped as known-reduced
+
+
 # ---------------------------------------------------------------------------------------------
 # acx_step_lengths pinned directly to the reference fixtures and to the oracle (VERDICT r04
 # item 3): the reference's carried lengths are ac_env.py:81-95 (self.lengths from reset, passed to
