@@ -50,14 +50,51 @@ def _devices(device):
     return [torch.device(device if device is not None else "cuda")]
 
 
-def _print_verbose_found(lib_found, h, path):
-    first = np.zeros(2, np.int32)
-    explored = ctypes.c_int64(0)
-    lib_found(h, first.ctypes.data, ctypes.byref(explored))
-    found = (np.array([first[0]], np.int8), np.array([first[1]], np.int8))
-    print(f"Found {found} after exploring {explored.value} nodes")  # greedy.py:92-99
-    print(f"Path to a trivial state: (tuples are of form (action, length of a state)) {path}")
-    print(f"Total path length: {len(path)}")
+def _read_result(lib, prefix, h, kw, max_nodes_to_explore, verbose, keep_node_keys, print_found):
+    """The result of a finished search through the `prefix`_{status,min_trace,node_keys,popped,
+    path,found} readers ("acx_greedy": csrc/acx_greedy.hip, "acx_search": csrc/acx_search.cpp; one
+    implementation, csrc/acx_frontier.h): LAST_STATS entries, the reference's prints, and
+    (solved, path)."""
+    fn = lambda name: getattr(lib, f"{prefix}_{name}")  # noqa: E731
+    budget = ctypes.c_int32(0)
+    min_len = ctypes.c_int32(0)
+    n_nodes = ctypes.c_int64(0)
+    status = fn("status")(h, ctypes.byref(budget), ctypes.byref(min_len), ctypes.byref(n_nodes))
+    LAST_STATS.update(nodes=int(n_nodes.value), status=int(status), min_length=int(min_len.value))
+    ntr = fn("min_trace")(h, None, 0)
+    trace = np.zeros(max(ntr, 1), np.int32)
+    fn("min_trace")(h, trace.ctypes.data, ntr)
+    LAST_STATS["min_trace"] = [int(v) for v in trace[:ntr]]
+    if keep_node_keys:
+        nk = np.zeros((n_nodes.value, kw), np.uint64)
+        fn("node_keys")(h, nk.ctypes.data, n_nodes.value)
+        LAST_STATS["node_keys"] = nk
+        npop = fn("popped")(h, None, 0)
+        pops = np.zeros(max(npop, 1), np.int64)
+        fn("popped")(h, pops.ctypes.data, npop)
+        LAST_STATS["popped"] = pops[:npop]
+    if verbose:  # greedy.py:86-89 / breadth_first.py:79-82, in the reference's order
+        for v in LAST_STATS["min_trace"]:
+            print(f"New minimal length found: {v}")
+    if status == 3:
+        raise AssertionError("a move produced an invalid presentation (utils.py:264-266)")
+    cap = 1 << 16
+    acts = np.zeros(cap, np.int32)
+    tots = np.zeros(cap, np.int32)
+    m = fn("path")(h, acts.ctypes.data, tots.ctypes.data, cap)
+    path = [(int(acts[i]), int(tots[i])) for i in range(min(m, cap))]
+    if verbose and status == 1 and print_found:  # greedy.py:92-99
+        first = np.zeros(2, np.int32)
+        explored = ctypes.c_int64(0)
+        fn("found")(h, first.ctypes.data, ctypes.byref(explored))
+        found = (np.array([first[0]], np.int8), np.array([first[1]], np.int8))
+        print(f"Found {found} after exploring {explored.value} nodes")
+        print(f"Path to a trivial state: (tuples are of form (action, length of a state)) {path}")
+        print(f"Total path length: {len(path)}")
+    if budget.value:
+        print(f"Exiting search as number of explored nodes = {n_nodes.value} has exceeded the limit "
+              f"{max_nodes_to_explore}")
+    return status == 1, path
 
 
 def run_greedy_device(p, max_nodes_to_explore, verbose, cyclical, device=None, batch=None, keep_node_keys=False):
@@ -77,45 +114,13 @@ def run_greedy_device(p, max_nodes_to_explore, verbose, cyclical, device=None, b
             _lib.check(st, "acx_greedy_run")
         stats = np.zeros(13, np.int64)
         lib.acx_greedy_stats(h, stats.ctypes.data)
-        budget = ctypes.c_int32(0)
-        min_len = ctypes.c_int32(0)
-        n_nodes = ctypes.c_int64(0)
-        status = lib.acx_greedy_status(h, ctypes.byref(budget), ctypes.byref(min_len), ctypes.byref(n_nodes))
         LAST_STATS.clear()
         LAST_STATS.update(rounds=int(stats[0]), expanded=int(stats[1]), pops=int(stats[2]),
                           device_known_children=int(stats[3]), host_select_s=stats[4] / 1e9,
                           gpu_roundtrip_s=stats[5] / 1e9, host_replay_s=stats[6] / 1e9, stop_new=int(stats[7]),
                           stop_old=int(stats[8]), stop_aged=int(stats[9]), gpu_wait_s=stats[10] / 1e9,
-                          host_cache_s=stats[11] / 1e9, retired_caches=int(stats[12]), nodes=int(n_nodes.value),
-                          status=int(status), min_length=int(min_len.value), engine="device-visited-set")
-        ntr = lib.acx_greedy_min_trace(h, None, 0)
-        trace = np.zeros(max(ntr, 1), np.int32)
-        lib.acx_greedy_min_trace(h, trace.ctypes.data, ntr)
-        LAST_STATS["min_trace"] = [int(v) for v in trace[:ntr]]
-        if keep_node_keys:
-            nk = np.zeros((n_nodes.value, kw), np.uint64)
-            lib.acx_greedy_node_keys(h, nk.ctypes.data, n_nodes.value)
-            LAST_STATS["node_keys"] = nk
-            npop = lib.acx_greedy_popped(h, None, 0)
-            pops = np.zeros(max(npop, 1), np.int64)
-            lib.acx_greedy_popped(h, pops.ctypes.data, npop)
-            LAST_STATS["popped"] = pops[:npop]
-        if verbose:  # greedy.py:86-89
-            for v in LAST_STATS["min_trace"]:
-                print(f"New minimal length found: {v}")
-        if status == 3:
-            raise AssertionError("a move produced an invalid presentation (utils.py:264-266)")
-        cap = 1 << 16
-        acts = np.zeros(cap, np.int32)
-        tots = np.zeros(cap, np.int32)
-        m = lib.acx_greedy_path(h, acts.ctypes.data, tots.ctypes.data, cap)
-        path = [(int(acts[i]), int(tots[i])) for i in range(min(m, cap))]
-        if verbose and status == 1:
-            _print_verbose_found(lib.acx_greedy_found, h, path)
-        if budget.value:
-            print(f"Exiting search as number of explored nodes = {n_nodes.value} has exceeded the limit "
-                  f"{max_nodes_to_explore}")
-        return status == 1, path
+                          host_cache_s=stats[11] / 1e9, retired_caches=int(stats[12]), engine="device-visited-set")
+        return _read_result(lib, "acx_greedy", h, kw, max_nodes_to_explore, verbose, keep_node_keys, True)
     finally:
         if h.value:
             lib.acx_greedy_destroy(h)
@@ -190,41 +195,6 @@ def run_search(mode, presentation, max_nodes_to_explore, verbose, cyclical, devi
         LAST_STATS.update(rounds=int(st[0]), expanded=int(st[1]), pops=int(st[2]), host_next_s=st[3] / 1e9,
                           host_store_s=st[4] / 1e9, host_replay_s=st[5] / 1e9, gpu_roundtrip_s=t_gpu,
                           kernel_s=sum(e0.elapsed_time(e1) for e0, e1 in kev) / 1e3)
-        budget = ctypes.c_int32(0)
-        min_len = ctypes.c_int32(0)
-        n_nodes = ctypes.c_int64(0)
-        status = lib.acx_search_status(h, ctypes.byref(budget), ctypes.byref(min_len), ctypes.byref(n_nodes))
-        LAST_STATS.update(nodes=int(n_nodes.value), status=int(status))
-        if keep_node_keys:
-            nk = np.zeros((n_nodes.value, kw), np.uint64)
-            lib.acx_search_node_keys(h, nk.ctypes.data, n_nodes.value)
-            LAST_STATS["node_keys"] = nk
-            npop = lib.acx_search_popped(h, None, 0)
-            pops = np.zeros(max(npop, 1), np.int64)
-            lib.acx_search_popped(h, pops.ctypes.data, npop)
-            LAST_STATS["popped"] = pops[:npop]
-        ntr = lib.acx_search_min_trace(h, None, 0)
-        trace = np.zeros(max(ntr, 1), np.int32)
-        lib.acx_search_min_trace(h, trace.ctypes.data, ntr)
-        LAST_STATS["min_trace"] = [int(v) for v in trace[:ntr]]
-        LAST_STATS["min_length"] = int(min_len.value)
-        if verbose:  # greedy.py:86-89 / breadth_first.py:79-82, in the reference's order
-            for v in LAST_STATS["min_trace"]:
-                print(f"New minimal length found: {v}")
-        if status == 3:
-            raise AssertionError("a move produced an invalid presentation (utils.py:264-266)")
-        cap = 1 << 16
-        acts = np.zeros(cap, np.int32)
-        tots = np.zeros(cap, np.int32)
-        m = lib.acx_search_path(h, acts.ctypes.data, tots.ctypes.data, cap)
-        path = [(int(acts[i]), int(tots[i])) for i in range(min(m, cap))]
-        if verbose and status == 1 and mode == GREEDY:
-            _print_verbose_found(lib.acx_search_found, h, path)
-        if budget.value:
-            print(
-                f"Exiting search as number of explored nodes = {n_nodes.value} has exceeded the limit "
-                f"{max_nodes_to_explore}"
-            )
-        return status == 1, path
+        return _read_result(lib, "acx_search", h, kw, max_nodes_to_explore, verbose, keep_node_keys, mode == GREEDY)
     finally:
         lib.acx_search_destroy(h)

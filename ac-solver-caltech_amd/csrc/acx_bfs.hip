@@ -896,7 +896,7 @@ int acx_bfs_run(void* h, const int32_t* presentation, int64_t max_nodes, int32_t
     Args& a = S->a;
     const int L = S->L, kw = S->kw;
     RootLaunch rl{S, st, {}};
-    pack_key(presentation, L, kw, rl.rk.w);
+    acx::pack_key(presentation, L, kw, rl.rk.w);
     int total0 = 0;
     for (int i = 0; i < 2 * L; ++i) total0 += presentation[i] != 0;
 

@@ -1,12 +1,13 @@
 // acx_bfs_common.h -- pieces shared by the single-GPU device BFS (acx_bfs.hip) and the
 // owner-partitioned multi-GPU BFS (acx_sbfs.hip): packed-key compare / hash, table entry
-// tags, block scans.
+// tags, block scans.  The key format itself (field readers, pack_key) is acx_key.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "acx.h"
+#include "acx_key.h"
 #include "acx_moves.h"
 
 namespace acx {
@@ -155,26 +156,6 @@ static void by_nw(int L, F&& f) {
         case 4: f.template go<4>(); break;
         default: f.template go<8>(); break;
     }
-}
-
-// host packing of a presentation into the key format (acx.h)
-static inline void pack_key(const int32_t* pres, int L, int kw, uint64_t* out) {
-    for (int k = 0; k < kw; ++k) out[k] = 0;
-    int n[2] = {0, 0};
-    for (int h = 0; h < 2; ++h) {
-        for (int i = 0; i < L; ++i) {
-            const int32_t v = pres[h * L + i];
-            if (v == 0) continue;
-            const uint64_t code = v == 1 ? 0 : v == -1 ? 1 : v == 2 ? 2 : 3;
-            const int bit = 2 * (h * L + i);
-            out[bit / 64] |= code << (bit % 64);
-            ++n[h];
-        }
-    }
-    const uint64_t lens = (uint64_t)n[0] | ((uint64_t)n[1] << 8);
-    const int bit = 4 * L;
-    out[bit / 64] |= lens << (bit % 64);
-    if (bit % 64 > 48 && bit / 64 + 1 < kw) out[bit / 64 + 1] |= lens >> (64 - bit % 64);
 }
 
 }  // namespace bfs

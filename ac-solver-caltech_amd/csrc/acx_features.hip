@@ -113,6 +113,8 @@ __global__ __launch_bounds__(TPB) void tokens_keys_kernel(const uint64_t* keys, 
     int64_t tok = 2;
     if (j < 2 * L) {
         const uint64_t* k = keys + i * kw;
+        // (inline: acx_key.h key_len) both length bytes from one 16-bit read, then the one of
+        // this element's relator: this unit does not include the search headers
         const int lb = 4 * L;
         const uint64_t lo = k[lb >> 6] >> (lb & 63);
         const uint64_t hi = (lb & 63) > 48 ? (k[(lb >> 6) + 1] << (64 - (lb & 63))) : 0ull;

@@ -18,6 +18,8 @@
 // its round (the in-flight conflicts), kept in a host table of the last 2^16..2^17 appended
 // nodes (two generations of tagged entries); children cached before the last 2^16 appends are
 // retired and their parent re-expanded with a later batch, which bounds that table.
+// The key format is acx_key.h; the priority key, the heaps, the in-flight table (Recent), the
+// per-child replay and the result readers are acx_frontier.h, shared with acx_search.cpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -31,6 +33,7 @@
 #include "acx_moves.h"
 
 #include "acx_bfs_common.h"
+#include "acx_frontier.h"
 
 namespace acx {
 namespace greedy {
@@ -41,10 +44,8 @@ using bfs::keq;
 using bfs::khash;
 using bfs::kload;
 
-constexpr int ACT = 12;
 constexpr int BUCKET = 8;
 constexpr uint32_t FP_MASK = 0xffffffu;
-constexpr int HDR = 40;  // priority-key header bits: total (9) | path length (31)
 constexpr int64_t AGE = 1 << 16;  // a cached expansion stays usable while fewer nodes than this have been
                                   // appended since its probe (bounds the in-flight table: two
                                   // generations of AGE nodes, 2 x 1 MB of tagged entries, cache-
@@ -195,10 +196,9 @@ static inline int64_t now_ns() {
         .count();
 }
 
-struct Engine {
+struct Engine : Outcome {
     int L = 0, kw = 0, pk = 0, cyc = 0, dev = 0;
     int64_t max_nodes = 0, cap = 0;
-    bool prio_generic = false;  // tests only (acx_internal_greedy_prio_key): the per-group priority key
     int64_t dcap = 0;  // nodes the device key store / visited set hold now (grown by doubling)
     uint64_t tsize = 0;
     int batch_cap = DEFAULT_BATCH;
@@ -215,31 +215,21 @@ struct Engine {
     std::vector<int64_t> c_known;
     std::vector<int32_t> c_round;
     std::vector<int32_t> free_slots;
-    // the recently appended nodes (the in-flight set), two generations of up to AGE ids each:
-    // gen[cur] holds ids >= gen_lo[cur], gen[cur ^ 1] the AGE ids before them; open addressing
-    // with entries (id + 1) << 16 | 16-bit tag, so a probe reads a node's key only on a tag hit
-    std::vector<uint64_t> gen[2];
-    int64_t gen_lo[2] = {0, 0};
-    int cur = 0;
-    uint64_t gmask = 0;
+    // the recently appended nodes (the in-flight set)
+    struct NodeKey {
+        const Engine* E;
+        const uint64_t* operator()(int64_t id) const { return &E->keys[(size_t)id * E->kw]; }
+    };
+    Recent<NodeKey> recent;
     std::vector<int64_t> n_at_round;  // round r: its kernel knew the ids below this; the host checks the rest
     int64_t committed = 0;            // ids < committed are in the device table
     int round = 0;
-    // result (greedy.py:86-121)
-    int status = 0;  // 0 running, 1 success, 2 failed, 3 move error
-    int budget_hit = 0;
-    int min_length = 0;
-    std::vector<int32_t> trace;
-    std::vector<int64_t> popped;
-    int64_t found_parent = -1, found_explored = 0, last_popped = -1;
-    int found_action = -1, last_action = -1, last_len = -1;
-    uint64_t found_key[ACX_MAX_L / 16 + 2] = {0};
     int64_t st_rounds = 0, st_expanded = 0, ns_select = 0, ns_gpu = 0, ns_replay = 0, st_known = 0;
     // why each round's replay stopped: the top node was appended during that replay / was an
     // older node outside the round's batch / had children cached too long ago
     int64_t st_stop_new = 0, st_stop_old = 0, st_stop_aged = 0;
-    int64_t ns_wait = 0, ns_cache = 0;
-    int64_t st_retired = 0;  // cached expansions retired unused because they aged  // inside the round trip: polling for the GPU / caching children
+    int64_t ns_wait = 0, ns_cache = 0;  // inside the round trip: polling for the GPU / caching children
+    int64_t st_retired = 0;             // cached expansions retired unused because they aged
     // staging: pinned host buffers the kernels read (parents + committed keys) and write (child
     // keys, hashes, known ids) directly, so a round is 2 launches and a completion poll -- no
     // copies, no blocking synchronisation
@@ -287,7 +277,7 @@ struct Engine {
     bool init(int L_, int64_t max_nodes_, int cyc_, int batch) {
         L = L_;
         kw = acx_key_words(L);
-        pk = (HDR + 6 * L + 63) / 64;
+        pk = prio_words(L);
         frontier.init(pk, &pkeys);
         unexpanded.init(pk, &pkeys);
         cyc = cyc_;
@@ -357,220 +347,14 @@ struct Engine {
     }
     void commit_launch();
 
-    // ---------------------------------------------------------------- key helpers
-    int len_field(const uint64_t* k, int h) const {
-        const int bit = 4 * L + 8 * h;
-        const uint64_t lo = k[bit >> 6] >> (bit & 63);
-        const uint64_t hi = (bit & 63) > 56 ? (k[(bit >> 6) + 1] << (64 - (bit & 63))) : 0ull;
-        return (int)((lo | hi) & 0xff);
-    }
-    int key_total(const uint64_t* k) const { return len_field(k, 0) + len_field(k, 1); }
-    bool key_is_error(const uint64_t* k) const { return len_field(k, 0) == 0xff && len_field(k, 1) == 0xff; }
-    uint32_t byte_at(const uint64_t* k, int bit) const {
-        const uint64_t lo = k[bit >> 6] >> (bit & 63);
-        const uint64_t hi = (bit & 63) > 56 ? (k[(bit >> 6) + 1] << (64 - (bit & 63))) : 0ull;
-        return (uint32_t)((lo | hi) & 0xff);
-    }
-
-    // the heap key: total (9 bits) | path length (31) | every letter + 2 in 3 bits, MSB first
-    // (x = 3, x^-1 = 1, y = 4, y^-1 = 0, padding = 2): unsigned word order = Python's tuple
-    // order of (total, path length, state tuple) (greedy.py:55-64,104-113)
-    void prio_key(const uint64_t* k, int tot, int dep, uint64_t* out) const {
-        static uint16_t tbl[256];
-        static bool init = false;
-        if (!init) {
-            static const uint32_t val[4] = {3, 1, 4, 0};
-            for (int b = 0; b < 256; ++b) {
-                uint32_t v = 0;
-                for (int j = 0; j < 4; ++j) v = (v << 3) | val[(b >> (2 * j)) & 3];
-                tbl[b] = (uint16_t)v;
-            }
-            init = true;
-        }
-        for (int i = 0; i < pk; ++i) out[i] = 0;
-        out[0] = ((uint64_t)(tot & 0x1ff) << 55) | ((uint64_t)(dep & 0x7fffffff) << 24);
-        int pos = HDR;
-        auto put = [&](uint64_t v, int nbits) {  // append nbits (<= 61) MSB-first
-            const int w = pos >> 6, o = pos & 63;
-            if (o + nbits <= 64) {
-                out[w] |= v << (64 - o - nbits);
-            } else {
-                out[w] |= v >> (o + nbits - 64);
-                out[w + 1] |= v << (128 - o - nbits);
-            }
-            pos += nbits;
-        };
-        constexpr uint64_t PAD20 = 0x492492492492492ull >> 0;  // 20 x 010 (60 bits): padding letters
-        if (L <= 40 && !prio_generic) {
-            // a relator's 2L code bits are taken in one 128-bit shift and mapped 4 letters per
-            // table lookup into two 60-bit parts (letters 0..19, 20..L-1); the padding letters'
-            // fields replaced by 010s with one mask per part -- a few appends instead of one per
-            // 4 letters (the general path below, which this reproduces bit for bit)
-            using u128 = unsigned __int128;
-            for (int h = 0; h < 2; ++h) {
-                const int n = len_field(k, h);
-                const int b0 = 2 * h * L, w = b0 >> 6, o = b0 & 63;
-                u128 codes = ((u128)k[w] | ((u128)(w + 1 < kw ? k[w + 1] : 0ull) << 64)) >> o;
-                if (o + 2 * L > 128 && w + 2 < kw) codes |= (u128)k[w + 2] << (128 - o);
-                auto part = [&](int f, int cnt) -> uint64_t {  // letters [f, f + cnt), cnt <= 20
-                    const int groups = (cnt + 3) / 4;
-                    uint64_t v = 0;
-                    for (int g = 0; g < groups; ++g) v = (v << 12) | tbl[(uint32_t)(codes >> (2 * f + 8 * g)) & 0xffu];
-                    v >>= 3 * (4 * groups - cnt);  // the letters past the part in its last group
-                    const int live = n - f < 0 ? 0 : (n - f > cnt ? cnt : n - f);
-                    if (live < cnt) {
-                        const uint64_t mask = (1ull << (3 * (cnt - live))) - 1;
-                        v = (v & ~mask) | (PAD20 & mask);
-                    }
-                    return v;
-                };
-                const int c0 = L < 20 ? L : 20;
-                put(part(0, c0), 3 * c0);
-                if (L > 20) put(part(20, L - 20), 3 * (L - 20));
-            }
-            return;
-        }
-        for (int h = 0; h < 2; ++h) {
-            const int n = len_field(k, h);
-            int i = 0;
-            for (; i + 4 <= n; i += 4) put(tbl[byte_at(k, 2 * (h * L + i))], 12);
-            for (; i < n; ++i) {
-                static const uint32_t val[4] = {3, 1, 4, 0};
-                put(val[byte_at(k, 2 * (h * L + i)) & 3], 3);
-            }
-            for (int m = L - n; m > 0; m -= 20) {
-                const int c = m < 20 ? m : 20;
-                put(PAD20 >> (3 * (20 - c)), 3 * c);
-            }
-        }
-    }
-
     // the nodes' heap keys (pk words per node id, prio_key), written once when a node is appended
     std::vector<uint64_t> pkeys;
-
-    // 4-ary min-heap of node ids ordered by their heap keys.  An entry is the key's first word
-    // (total | path length | the first 24 letter bits: nearly always decides) and the id, 16 bytes;
-    // the rest of the key is read from pkeys only on a tie of first words.  (Round 5's entries
-    // held the whole key inline, 8 + 8 * pk bytes, copied at every level of a sift.)
-    struct Heap {
-        struct Ent {
-            uint64_t k0;
-            int64_t id;
-        };
-        int pk = 0;
-        const std::vector<uint64_t>* keys = nullptr;  // Engine::pkeys
-        std::vector<Ent> e;
-        bool less(const Ent& x, const Ent& y) const {
-            if (x.k0 != y.k0) return x.k0 < y.k0;
-            const uint64_t* a = keys->data() + (size_t)x.id * pk;
-            const uint64_t* b = keys->data() + (size_t)y.id * pk;
-            for (int i = 1; i < pk; ++i)
-                if (a[i] != b[i]) return a[i] < b[i];
-            return false;
-        }
-        bool empty() const { return e.empty(); }
-        size_t size() const { return e.size(); }
-        int64_t top() const { return e[0].id; }
-        void push(uint64_t k0, int64_t v) {
-            size_t i = e.size();
-            e.push_back(Ent{k0, v});
-            const Ent x{k0, v};
-            while (i > 0) {
-                const size_t par = (i - 1) / 4;
-                if (!less(x, e[par])) break;
-                e[i] = e[par];
-                i = par;
-            }
-            e[i] = x;
-        }
-        void pop() {
-            const size_t n = e.size() - 1;
-            const Ent x = e[n];
-            e.pop_back();
-            if (n == 0) return;
-            size_t i = 0;
-            while (true) {
-                const size_t c0 = 4 * i + 1;
-                if (c0 >= n) break;
-                size_t best = c0;
-                const size_t ce = c0 + 4 < n ? c0 + 4 : n;
-                for (size_t c = c0 + 1; c < ce; ++c)
-                    if (less(e[c], e[best])) best = c;
-                if (!less(e[best], x)) break;
-                e[i] = e[best];
-                i = best;
-            }
-            e[i] = x;
-        }
-    };
-    // one heap per total (the priority key's top 9 bits): a pop sifts through the nodes of the
-    // smallest total only, not the whole frontier (10^6 nodes: ~10 cold levels per pop); the order
-    // is the single heap's, since the total is the key's most significant field
-    struct BucketHeap {
-        static constexpr int NB = 512;
-        int minb = NB;  // the smallest non-empty bucket (NB: none)
-        size_t n = 0;
-        std::vector<Heap> b;
-        void init(int pk, const std::vector<uint64_t>* keys) {
-            b.assign(NB, Heap{});
-            for (Heap& h : b) {
-                h.pk = pk;
-                h.keys = keys;
-            }
-            minb = NB;
-            n = 0;
-        }
-        bool empty() const { return n == 0; }
-        size_t size() const { return n; }
-        void push(uint64_t k0, int64_t v) {
-            const int i = (int)(k0 >> 55);
-            b[(size_t)i].push(k0, v);
-            if (i < minb) minb = i;
-            ++n;
-        }
-        int64_t top() const { return b[(size_t)minb].top(); }
-        void pop() {
-            b[(size_t)minb].pop();
-            --n;
-            while (minb < NB && b[(size_t)minb].empty()) ++minb;
-        }
-    };
     BucketHeap frontier;  // every node not popped yet: the reference's to_explore (pop order)
     // cached expansions in round order, to retire the ones that aged (their node then counts as
     // unexpanded again and is picked up by select() with the other smallest unexpanded nodes)
     std::vector<std::pair<int32_t, int64_t>> cache_fifo;
     size_t fifo_head = 0;
     BucketHeap unexpanded;  // the frontier nodes without usable cached children (expansion order)
-
-    // ---------------------------------------------------------------- in-flight table
-    static uint64_t tag_of(uint64_t h) { return (h >> 48) & 0xffffu; }
-    void recent_insert(int64_t id, uint64_t h) {
-        if (id - gen_lo[cur] >= age) {  // the current generation is full: it becomes the older one
-            cur ^= 1;
-            std::fill(gen[cur].begin(), gen[cur].end(), 0ull);
-            gen_lo[cur] = id;
-        }
-        std::vector<uint64_t>& g = gen[cur];
-        uint64_t s = h & gmask;
-        while (g[s]) s = (s + 1) & gmask;
-        g[s] = ((uint64_t)(id + 1) << 16) | tag_of(h);
-    }
-    // a node with id >= from equal to key k, or -1 (from >= the older generation's first id:
-    // usable() admits only caches probed fewer than AGE appends ago)
-    int64_t recent_find(const uint64_t* k, uint64_t h, int64_t from) const {
-        const uint64_t tag = tag_of(h);
-        for (int i = 0; i < 2; ++i) {
-            const int gi = cur ^ i;
-            if (i == 1 && gen_lo[cur] <= from) break;  // every id >= from is in the current one
-            const std::vector<uint64_t>& g = gen[gi];
-            for (uint64_t s = h & gmask; g[s]; s = (s + 1) & gmask) {
-                if ((g[s] & 0xffffu) != tag) continue;
-                const int64_t id = (int64_t)(g[s] >> 16) - 1;
-                if (id >= from && memcmp(&keys[(size_t)id * kw], k, 8 * kw) == 0) return id;
-            }
-        }
-        return -1;
-    }
 
     int64_t add_node(const uint64_t* k, uint64_t h, int64_t par, int act, int tot, int dep) {
         const int64_t id = (int64_t)parent.size();
@@ -580,10 +364,10 @@ struct Engine {
         total.push_back((int16_t)tot);
         depth.push_back(dep);
         cache_slot.push_back(-1);
-        recent_insert(id, h);
+        recent.insert(id, h);
         pkeys.resize(pkeys.size() + pk);
         uint64_t* pkey = &pkeys[(size_t)id * pk];
-        prio_key(k, tot, dep, pkey);
+        prio_key(k, L, kw, pk, tot, dep, pkey);
         frontier.push(pkey[0], id);
         unexpanded.push(pkey[0], id);
         return id;
@@ -591,7 +375,7 @@ struct Engine {
 
     // A cached expansion is usable while the whole visit stays inside the in-flight table's
     // reach: the visit appends up to ACT nodes, and an append that starts a new generation
-    // keeps only the `age` ids before it (recent_insert), so every id >= `from` must still be
+    // keeps only the `age` ids before it (Recent::insert), so every id >= `from` must still be
     // there after the visit's last append: parent.size() + ACT - from <= age.
     bool usable(int64_t id) const {
         const int32_t s = cache_slot[id];
@@ -606,56 +390,26 @@ struct Engine {
     }
 
     // ---------------------------------------------------------------- one popped node
+    // a child is already a node if the device knew it as of the probe, or it was appended since
     bool visit(int64_t id) {
         const int32_t s = cache_slot[id];
-        const uint64_t* ck = &c_keys[(size_t)s * ACT * kw];
-        const uint64_t* hs = &c_hash[(size_t)s * ACT];
         const int64_t* kn = &c_known[(size_t)s * ACT];
         const int64_t from = n_at_round[c_round[s]];
-        last_popped = id;
-        popped.push_back(id);
-        bool ended = false;
-        for (int a = 0; a < ACT; ++a) {
-            const uint64_t* k = ck + (size_t)a * kw;
-            if (key_is_error(k)) {  // ACMove raised (utils.py:264-266)
-                status = 3;
-                ended = true;
-                break;
-            }
-            const int len = key_total(k);
-            last_action = a;
-            last_len = len;
-            if (len < min_length) {  // greedy.py:86-89
-                min_length = len;
-                trace.push_back(len);
-            }
-            if (len == 2) {  // greedy.py:91-100
-                status = 1;
-                found_parent = id;
-                found_action = a;
-                found_explored = (int64_t)parent.size() - (int64_t)frontier.size();
-                memcpy(found_key, k, 8 * kw);
-                ended = true;
-                break;
-            }
-            // greedy.py:102-113: known to the device as of the probe, or appended since
-            if (kn[a] >= 0) {
-                ++st_known;
-                continue;
-            }
-            if (recent_find(k, hs[a], from) >= 0) continue;
-            add_node(k, hs[a], id, a, len, depth[id] + 1);
-        }
+        const bool ended = replay_children(
+            &c_keys[(size_t)s * ACT * kw], &c_hash[(size_t)s * ACT], L, kw, *this, id, (int64_t)parent.size(),
+            (int64_t)frontier.size(), max_nodes,
+            [&](const uint64_t* k, uint64_t h, int a) {
+                if (kn[a] >= 0) {
+                    ++st_known;
+                    return true;
+                }
+                return recent.find(k, h, from) >= 0;
+            },
+            [&](const uint64_t* k, uint64_t h, int a, int len) { add_node(k, h, id, a, len, depth[id] + 1); });
         drop_cache(id);
-        if (!ended && (int64_t)parent.size() >= max_nodes) {  // greedy.py:115-119
-            status = 2;
-            budget_hit = 1;
-            ended = true;
-        }
         return ended;
     }
 
-    // the smallest frontier nodes without usable cached children (greedy expands them next)
     void push_unexpanded(int64_t id) { unexpanded.push(pkeys[(size_t)id * pk], id); }
 
     // the smallest frontier nodes without usable cached children (greedy expands them next)
@@ -687,7 +441,7 @@ struct Engine {
     int run(const int32_t* pres) {
         // the root: the (unreduced) input presentation itself (greedy.py:36-68)
         uint64_t root[ACX_MAX_L / 16 + 2];
-        bfs::pack_key(pres, L, kw, root);
+        pack_key(pres, L, kw, root);
         int tot0 = 0;
         for (int i = 0; i < 2 * L; ++i) tot0 += pres[i] != 0;
         min_length = tot0;
@@ -700,19 +454,16 @@ struct Engine {
         // every per-node array at its final size up front (no reallocation copies mid-search)
         const size_t nres = (size_t)std::min<int64_t>(cap, 1 << 26);
         keys.reserve(nres * kw);
-        for (auto* v : {&parent}) v->reserve(nres);
+        parent.reserve(nres);
         action.reserve(nres);
         total.reserve(nres);
         depth.reserve(nres);
         cache_slot.reserve(nres);
-        for (auto& g : gen) g.assign((size_t)2 * age, 0ull);
-        gmask = 2 * age - 1;
-        cur = 0;
-        gen_lo[0] = gen_lo[1] = 0;
-        recent_insert(0, host_hash(root, kw));
+        recent = Recent<NodeKey>(age, kw, NodeKey{this});
+        recent.insert(0, host_hash(root, kw));
         pkeys.assign(pk, 0ull);
         pkeys.reserve(nres * pk);
-        prio_key(root, tot0, 0, pkeys.data());
+        prio_key(root, L, kw, pk, tot0, 0, pkeys.data());
         frontier.push(pkeys[0], 0);
         unexpanded.push(pkeys[0], 0);
         std::vector<int64_t> batch;
@@ -853,6 +604,7 @@ int Engine::expand_round(const std::vector<int64_t>& batch) {
 }  // namespace greedy
 }  // namespace acx
 
+using namespace acx;
 using namespace acx::greedy;
 
 extern "C" {
@@ -887,43 +639,20 @@ void acx_internal_greedy_init_cap(int32_t log2_cap) { g_dcap_override = log2_cap
 int32_t acx_internal_greedy_prio_key(int32_t L, const uint64_t* key, int32_t total, int32_t depth, uint64_t* out,
                                      int32_t generic) {
     if (L < 1 || L > ACX_MAX_L || !key || !out) return -1;
-    Engine e;
-    e.L = L;
-    e.kw = acx_key_words(L);
-    e.pk = (HDR + 6 * L + 63) / 64;
-    e.prio_generic = generic != 0;
-    e.prio_key(key, total, depth, out);
-    return e.pk;
+    const int pk = prio_words(L);
+    prio_key(key, L, acx_key_words(L), pk, total, depth, out, generic != 0);
+    return pk;
 }
 
 // 0 running, 1 success, 2 failed, 3 move error; budget_hit, min_length, nodes (len(tree_nodes))
 int32_t acx_greedy_status(void* h, int32_t* budget_hit, int32_t* min_length, int64_t* n_nodes) {
     Engine* E = static_cast<Engine*>(h);
-    if (budget_hit) *budget_hit = E->budget_hit;
-    if (min_length) *min_length = E->min_length;
-    if (n_nodes) *n_nodes = (int64_t)E->parent.size();
-    return E->status;
+    return read_status(*E, (int64_t)E->parent.size(), budget_hit, min_length, n_nodes);
 }
 
-// the returned path: success -> the found child's; otherwise the last popped node's plus its
-// last child (greedy.py:100,121).  Returns the number of (action, total) entries.
 int64_t acx_greedy_path(void* h, int32_t* actions, int32_t* totals, int64_t cap) {
     Engine* E = static_cast<Engine*>(h);
-    const int64_t v0 = E->status == 1 ? E->found_parent : E->last_popped;
-    if (v0 < 0) return 0;
-    std::vector<int64_t> chain;
-    for (int64_t v = v0; v >= 0; v = E->parent[v]) chain.push_back(v);
-    int64_t n = 0;
-    for (auto it = chain.rbegin(); it != chain.rend(); ++it, ++n)
-        if (n < cap) {
-            actions[n] = E->action[*it];
-            totals[n] = E->total[*it];
-        }
-    if (n < cap) {
-        actions[n] = E->status == 1 ? E->found_action : E->last_action;
-        totals[n] = E->status == 1 ? 2 : E->last_len;
-    }
-    return n + 1;
+    return read_path(*E, E->parent.data(), E->action.data(), E->total.data(), actions, totals, cap);
 }
 
 // out[0] rounds, [1] parents expanded, [2] parents popped, [3] children the device knew,
@@ -950,36 +679,22 @@ void acx_greedy_stats(void* h, int64_t* out) {
 
 int64_t acx_greedy_min_trace(void* h, int32_t* out, int64_t cap) {
     Engine* E = static_cast<Engine*>(h);
-    const int64_t n = (int64_t)E->trace.size();
-    for (int64_t i = 0; out && i < n && i < cap; ++i) out[i] = E->trace[(size_t)i];
-    return n;
+    return read_array(E->trace.data(), (int64_t)E->trace.size(), out, cap);
 }
 
 int64_t acx_greedy_popped(void* h, int64_t* ids, int64_t cap) {
     Engine* E = static_cast<Engine*>(h);
-    const int64_t n = (int64_t)E->popped.size();
-    for (int64_t i = 0; ids && i < n && i < cap; ++i) ids[i] = E->popped[(size_t)i];
-    return n;
+    return read_array(E->popped.data(), (int64_t)E->popped.size(), ids, cap);
 }
 
 int64_t acx_greedy_node_keys(void* h, uint64_t* out, int64_t cap) {
     Engine* E = static_cast<Engine*>(h);
-    const int64_t n = (int64_t)E->parent.size();
-    if (out) memcpy(out, E->keys.data(), (size_t)(n < cap ? n : cap) * E->kw * 8);
-    return n;
+    return read_array(E->keys.data(), (int64_t)E->parent.size(), out, cap, E->kw);
 }
 
 int32_t acx_greedy_found(void* h, int32_t* first_letters, int64_t* explored) {
     Engine* E = static_cast<Engine*>(h);
-    if (E->status != 1) return 0;
-    static const int32_t letter[4] = {1, -1, 2, -2};
-    const int bit1 = 2 * E->L;
-    if (first_letters) {
-        first_letters[0] = letter[E->found_key[0] & 3u];
-        first_letters[1] = letter[(E->found_key[bit1 >> 6] >> (bit1 & 63)) & 3u];
-    }
-    if (explored) *explored = E->found_explored;
-    return 1;
+    return read_found(*E, E->L, first_letters, explored);
 }
 
 }  // extern "C"

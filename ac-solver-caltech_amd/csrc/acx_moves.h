@@ -382,6 +382,8 @@ struct PresRegs {
 };
 
 // packed key: r0 letters, r1 letters, n0 (8 bits), n1 (8 bits); KW64 uint64 words
+// (inline: acx_key.h states this format for pointers to 64-bit words; make_key / load_key build
+// and split it in registers, as shifts of 32-bit Word<> limbs by 2L and 4L)
 // the packed key in registers: out[k] for k < NW + 1 (words >= kw64 are zero)
 template <int NW>
 __device__ __forceinline__ void make_key(int L, const PresRegs<NW>& p, uint64_t (&out)[NW + 1]) {

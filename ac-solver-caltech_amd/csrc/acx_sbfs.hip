@@ -623,19 +623,6 @@ __global__ __launch_bounds__(TPB) void sbfs_minlen_kernel(Args a, int64_t last, 
     if (threadIdx.x == 0 && v != NONE) atomicMin(&a.ctl->min_len, v);
 }
 
-// the total length stored in a packed child key (n0 at bit 4L, n1 at bit 4L + 8)
-__device__ __forceinline__ uint32_t key_total(const uint64_t* k, int L) {
-    uint32_t t = 0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int bit = 4 * L + 8 * h, w = bit >> 6, o = bit & 63;
-        uint64_t v = k[w] >> o;
-        if (o > 56) v |= k[w + 1] << (64 - o);
-        t += (uint32_t)(v & 0xffu);
-    }
-    return t;
-}
-
 // verbose trace (breadth_first.py:79-82): this rank's chunk children with seq < end whose total
 // is below every earlier child of this rank and below `running` -- the rank's prefix minima, a
 // superset of the global new minima that lie on this rank (<= 2L of them).  One block: a min
@@ -651,7 +638,7 @@ __global__ __launch_bounds__(1024) void sbfs_trace_kernel(Args a, int npar, uint
     const int per = (npar + 1023) / 1024;
     const int j0 = min(npar, t * per), j1 = min(npar, j0 + per);
     auto child_total = [&](int j, int act) -> uint32_t {
-        return key_total(a.ckeys + ((int64_t)j * 12 + act) * a.kw, a.L);
+        return (uint32_t)key_total(a.ckeys + ((int64_t)j * 12 + act) * a.kw, a.L);
     };
     auto parent_seq = [&](int j) -> uint32_t { return (uint32_t)(a.lgid[a.lo + j] - a.head) * 12u; };
     uint32_t mn = NONE;
@@ -985,7 +972,7 @@ int32_t acx_sbfs_owner(const int32_t* presentation, int32_t L, int32_t world) {
     constexpr int KM = ACX_MAX_L / 16 + 2;
     const int kw = acx_key_words(L);
     Key<KM> k{};
-    pack_key(presentation, L, kw, k.w);
+    acx::pack_key(presentation, L, kw, k.w);
     const uint64_t hv = khash<KM>(k, kw);
     return (int32_t)(((hv >> 32) * (uint64_t)world) >> 32);
 }
@@ -1013,7 +1000,7 @@ int acx_sbfs_reset(void* h, const int32_t* presentation, void* stream) {
     sbfs_ctl_init_kernel<<<dim3(1), dim3(64), 0, st>>>(S->a.ctl);
     if (own == S->rank) {
         RootLaunch rl{S, st, {}};
-        pack_key(presentation, S->L, S->kw, rl.rk.w);
+        acx::pack_key(presentation, S->L, S->kw, rl.rk.w);
         by_nw(S->L, rl);
         S->nloc = 1;
         S->abase = 1;  // the root's record

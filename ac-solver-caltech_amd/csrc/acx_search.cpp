@@ -11,8 +11,10 @@
 //   * greedy: priority order (total length, path length, state tuple) -- a total order,
 //     so heapq's pop sequence equals popping a min-heap on that order (greedy.py:71-113).  The smallest not-yet-expanded nodes are expanded
 //     speculatively in one launch; children are cached until their parent is popped.
-// Keys are the packed states of acx_expand12 (acx.h), so set membership is a hash of
-// acx_key_words(L) uint64 words.
+// Keys are the packed states of acx_expand12 (acx.h, read through acx_key.h), so set membership
+// is a hash of acx_key_words(L) uint64 words.  Greedy's priority key, its ordered frontier
+// (BucketHeap), the per-child replay of a popped node and the result readers are
+// acx_frontier.h, shared with the device-visited-set engine (acx_greedy.hip).
 #include <sched.h>
 #include <sys/mman.h>
 
@@ -29,8 +31,12 @@
 #include <vector>
 
 #include "acx.h"
+#include "acx_frontier.h"
+#include "acx_key.h"
 
 namespace {
+
+using namespace acx;
 
 // A fixed set of worker threads for the BFS batch phases: run(fn) calls fn(t) for t = 0..T-1,
 // t = 0 on the calling thread, and returns when all are done.
@@ -140,9 +146,6 @@ int host_threads() {
     return n < 1 ? 1 : (n > 16 ? 16 : n);
 }
 
-constexpr int ACT = 12;
-constexpr int HDR = 40;         // priority-key header bits: total (9) | depth (31)
-
 inline uint64_t mix64(uint64_t x) {
     x ^= x >> 30;
     x *= 0xbf58476d1ce4e5b9ull;
@@ -152,7 +155,7 @@ inline uint64_t mix64(uint64_t x) {
     return x;
 }
 
-struct Engine {
+struct Engine : Outcome {
     int mode;  // 0 bfs, 1 greedy
     int L, kw;
     int64_t max_nodes;
@@ -167,95 +170,23 @@ struct Engine {
     std::vector<uint64_t> table;
     uint64_t mask = 0;
     int64_t n_set = 0;
-    // greedy's expansion bookkeeping (BFS: every node is queued once, when it is found, so the
-    // FIFO queue is the node ids in order -- queue[i] == i -- and is not stored)
-    std::vector<int64_t> queue;
+    // expansion bookkeeping.  BFS: every node is queued once, when it is found, so the FIFO queue
+    // is the node ids in order and is not stored: [head, requested) are out for expansion
     size_t head = 0, requested = 0;
-    // greedy ordered frontier: the heap tuple (total, path length, state tuple) of
-    // greedy.py:55-64,104-113 packed MSB-first into pk words per node -- total (9 bits: up to
-    // 2L = 256), depth (31 bits), then every letter + 2 (3 bits, r0 then r1 incl. padding) --
-    // so comparing the words as unsigned integers is Python's tuple order.  Two 4-ary min-heaps
-    // with the keys inline (no pointer chasing per comparison): all unpopped nodes (pop
-    // order) and the subset not yet sent to the GPU (speculative expansion order).
+    // greedy: the nodes' priority keys (pk words per node id, prio_key) and two ordered frontiers
+    // over them: all unpopped nodes (pop order) and the subset not yet sent to the GPU
+    // (speculative expansion order)
     int pk = 0;
-    struct Heap {
-        int pk = 0;
-        std::vector<uint64_t> k;  // size() * pk key words
-        std::vector<int64_t> id;
-        bool empty() const { return id.empty(); }
-        int64_t top() const { return id[0]; }
-        bool less(const uint64_t* a, const uint64_t* b) const {
-            for (int i = 0; i < pk; ++i)
-                if (a[i] != b[i]) return a[i] < b[i];
-            return false;
-        }
-        void push(const uint64_t* key, int64_t v) {
-            size_t i = id.size();
-            id.push_back(v);
-            k.resize(k.size() + pk);
-            uint64_t tmp[32];
-            std::memcpy(tmp, key, sizeof(uint64_t) * pk);
-            while (i > 0) {
-                const size_t par = (i - 1) / 4;
-                if (!less(tmp, &k[par * pk])) break;
-                std::memcpy(&k[i * pk], &k[par * pk], sizeof(uint64_t) * pk);
-                id[i] = id[par];
-                i = par;
-            }
-            std::memcpy(&k[i * pk], tmp, sizeof(uint64_t) * pk);
-            id[i] = v;
-        }
-        void pop() {
-            const size_t n = id.size() - 1;
-            if (n == 0) {
-                id.clear();
-                k.clear();
-                return;
-            }
-            uint64_t tmp[32];
-            std::memcpy(tmp, &k[n * pk], sizeof(uint64_t) * pk);
-            const int64_t v = id[n];
-            id.pop_back();
-            k.resize(n * pk);
-            size_t i = 0;
-            while (true) {
-                const size_t c0 = 4 * i + 1;
-                if (c0 >= n) break;
-                size_t best = c0;
-                const size_t ce = c0 + 4 < n ? c0 + 4 : n;
-                for (size_t c = c0 + 1; c < ce; ++c)
-                    if (less(&k[c * pk], &k[best * pk])) best = c;
-                if (!less(&k[best * pk], tmp)) break;
-                std::memcpy(&k[i * pk], &k[best * pk], sizeof(uint64_t) * pk);
-                id[i] = id[best];
-                i = best;
-            }
-            std::memcpy(&k[i * pk], tmp, sizeof(uint64_t) * pk);
-            id[i] = v;
-        }
-    };
-    Heap frontier;    // pop order (all unpopped nodes)
-    Heap unexpanded;  // the subset not yet sent to the GPU
+    std::vector<uint64_t> pkeys;
+    BucketHeap frontier, unexpanded;
     // children cache: node -> offset into cache_keys (ACT * kw words), -1 = not cached
     std::vector<int64_t> cache_pos;
     bool cached(int64_t id) const { return cache_pos[id] >= 0; }
     std::vector<uint64_t> cache_keys;
-    std::vector<uint64_t> cache_hash;  // ACT hashes per slot (computed once, reused for prefetch)
+    std::vector<uint64_t> cache_hash;  // ACT hashes per slot
     std::vector<size_t> free_slots;
     // last request (order of nodes handed to next_batch)
     std::vector<int64_t> batch;
-    // result
-    int status = 0;  // 0 running, 1 success, 2 failed (budget or exhausted), 3 move error
-    int64_t found_parent = -1;
-    int found_action = -1, found_len = -1;
-    int last_action = -1, last_len = -1;
-    int64_t last_popped = -1;
-    int min_length = 0;
-    int budget_hit = 0;
-    std::vector<int32_t> trace;  // each new minimum total, in the order found (greedy.py:86-89)
-    std::vector<int64_t> popped; // node ids in expansion (pop) order
-    int64_t found_explored = 0;  // len(tree_nodes) - len(to_explore) at the success (greedy.py:94)
-    uint64_t found_key[ACX_MAX_L / 16 + 2] = {0};
     // statistics: rounds (next_batch calls that returned parents), parents expanded, pops
     int64_t st_rounds = 0, st_expanded = 0, st_pops = 0;
     int64_t ns_next = 0, ns_store = 0, ns_visit = 0;  // host time in next_batch / caching children / replay
@@ -293,8 +224,9 @@ struct Engine {
     Engine(int mode_, int L_, int64_t max_nodes_) : mode(mode_), L(L_), kw(acx_key_words(L_)), max_nodes(max_nodes_) {
         table.assign(1 << 12, 0);
         mask = table.size() - 1;
-        pk = (HDR + 6 * L + 63) / 64;
-        frontier.pk = unexpanded.pk = pk;
+        pk = prio_words(L);
+        frontier.init(pk, &pkeys);
+        unexpanded.init(pk, &pkeys);
         if (mode == 0) {
             n_threads = host_threads();
             pool = new Pool(n_threads);
@@ -380,54 +312,6 @@ struct Engine {
             p = (p + 1) & mask;
         }
     }
-    void prefetch_children(int64_t id) const {
-        if (!cached(id)) return;
-        const uint64_t* hs = &cache_hash[(size_t)cache_pos[id] / kw];
-        for (int a = 0; a < ACT; ++a) __builtin_prefetch(&table[hs[a] & mask], 0, 1);
-    }
-    static int key_len(const uint64_t* k, int L) {
-        const int bit = 4 * L;
-        const uint64_t lo = k[bit >> 6] >> (bit & 63);
-        const uint64_t hi = (bit & 63) > 48 ? (k[(bit >> 6) + 1] << (64 - (bit & 63))) : 0ull;
-        const uint64_t v = lo | hi;
-        return (int)(v & 0xff) + (int)((v >> 8) & 0xff);
-    }
-    // acx_expand12's key for a child whose move failed: both length bytes 0xFF
-    static bool key_is_error(const uint64_t* k, int L) {
-        const int bit = 4 * L;
-        const uint64_t lo = k[bit >> 6] >> (bit & 63);
-        const uint64_t hi = (bit & 63) > 48 ? (k[(bit >> 6) + 1] << (64 - (bit & 63))) : 0ull;
-        return ((lo | hi) & 0xffffull) == 0xffffull;
-    }
-    // the packed priority key of a node (see Heap)
-    void prio_key(const uint64_t* k, int tot, int dep, uint64_t* out) const {
-        int n[2];
-        {
-            const int bit = 4 * L;
-            const uint64_t lo = k[bit >> 6] >> (bit & 63);
-            const uint64_t hi = (bit & 63) > 48 ? (k[(bit >> 6) + 1] << (64 - (bit & 63))) : 0ull;
-            n[0] = (int)((lo | hi) & 0xff);
-            n[1] = (int)(((lo | hi) >> 8) & 0xff);
-        }
-        for (int i = 0; i < pk; ++i) out[i] = 0;
-        out[0] = ((uint64_t)(tot & 0x1ff) << 55) | ((uint64_t)(dep & 0x7fffffff) << 24);
-        static const uint64_t val[4] = {3, 1, 4, 0};  // letter + 2 for codes x, x^-1, y, y^-1
-        int pos = HDR;  // next free bit, counted from the MSB of word 0
-        for (int h = 0; h < 2; ++h)
-            for (int i = 0; i < L; ++i, pos += 3) {
-                const int bit = 2 * (h * L + i);
-                const int code = (int)((k[bit >> 6] >> (bit & 63)) & 3u);
-                const uint64_t v = i < n[h] ? val[code] : 2;  // padding 0 -> 2
-                // 3 bits at MSB-first position pos (may straddle two words)
-                const int w = pos >> 6, o = pos & 63;
-                if (o <= 61) {
-                    out[w] |= v << (61 - o);
-                } else {
-                    out[w] |= v >> (o - 61);
-                    out[w + 1] |= v << (64 - (o - 61));
-                }
-            }
-    }
     int64_t add_node(const uint64_t* k, uint64_t h, uint64_t slot, int64_t par, int act, int tot, int dep) {
         const int64_t id = (int64_t)parent.size();
         keys.insert(keys.end(), k, k + kw);
@@ -443,16 +327,17 @@ struct Engine {
     }
 
     void push_frontier(int64_t id, const uint64_t* k) {
-        uint64_t key[32];
-        prio_key(k, total[id], depth[id], key);
-        frontier.push(key, id);
-        unexpanded.push(key, id);
+        pkeys.resize(pkeys.size() + pk);
+        uint64_t* pkey = &pkeys[(size_t)id * pk];
+        prio_key(k, L, kw, pk, total[id], depth[id], pkey);
+        frontier.push(pkey[0], id);
+        unexpanded.push(pkey[0], id);
     }
 
     void start(const uint64_t* k) {
         uint64_t slot = 0;
         const uint64_t h = hash_key(k);
-        const int tot = key_len(k, L);
+        const int tot = key_total(k, L);
         min_length = tot;
         if (mode == 0) {  // the root in its partition of the visited set
             Part& P = parts[owner(h)];
@@ -513,61 +398,25 @@ struct Engine {
         cache_pos[id] = (int64_t)off;
     }
 
-    // expand one popped node from its cached children; returns true when the search ends
+    // greedy: expand one popped node from its cached children; returns true when the search ends
     bool visit(int64_t id) {
         const size_t off = (size_t)cache_pos[id];
-        const uint64_t* ck = &cache_keys[off];
-        const uint64_t* hs = &cache_hash[off / kw];
-        last_popped = id;
         ++st_pops;
-        popped.push_back(id);
-        bool ended = false;
-        for (int a = 0; a < ACT && !ended; ++a) {
-            const uint64_t* k = ck + (size_t)a * kw;
-            if (key_is_error(k, L)) {  // ACMove raised (utils.py:264-266) before any test
-                status = 3;
-                ended = true;
-                break;
-            }
-            const int len = key_len(k, L);
-            last_action = a;
-            last_len = len;
-            if (len < min_length) {
-                min_length = len;
-                trace.push_back(len);
-            }
-            if (len == 2) {  // greedy.py:91, breadth_first.py:84
-                status = 1;
-                found_parent = id;
-                found_action = a;
-                found_len = len;
-                found_explored = n_set - (int64_t)frontier.id.size();
-                std::memcpy(found_key, k, sizeof(uint64_t) * kw);
-                ended = true;
-                break;
-            }
-            uint64_t slot = 0;
-            if (find(k, hs[a], &slot) < 0) {
-                const int64_t nid = add_node(k, hs[a], slot, id, a, len, depth[id] + 1);
-                if (mode == 0) queue.push_back(nid);
-                else {
-                    push_frontier(nid, k);
-                }
-            }
-        }
+        uint64_t slot = 0;  // where the child that was just looked up goes
+        const bool ended = replay_children(
+            &cache_keys[off], &cache_hash[off / kw], L, kw, *this, id, n_set, (int64_t)frontier.size(), max_nodes,
+            [&](const uint64_t* k, uint64_t h, int) { return find(k, h, &slot) >= 0; },
+            [&](const uint64_t* k, uint64_t h, int a, int len) {
+                push_frontier(add_node(k, h, slot, id, a, len, depth[id] + 1), k);
+            });
         cache_pos[id] = -1;
         free_slots.push_back(off);
-        if (!ended && n_set >= max_nodes) {  // greedy.py:115, breadth_first.py:91
-            status = 2;
-            budget_hit = 1;
-            ended = true;
-        }
         return ended;
     }
 
     // BFS: the fed batch = the parents queue[head, head + P) in FIFO order, their children (P, 12,
     // kw) in the reference's order (parent, then action: sequence number c = 12 g + a).  Same
-    // result as visiting them one by one (visit()):
+    // result as visiting them one by one (replay_children in acx_frontier.h):
     //   1. (threads, by child) hash, total length / move error, owner partition;
     //   2. (one thread) the first move error and the first success in sequence order, and the
     //      new minimum totals up to there (breadth_first.py:76-89);
@@ -593,7 +442,7 @@ struct Engine {
                 const uint64_t* k = ck + (size_t)c * kw;
                 const uint64_t h = hash_key(k);
                 b_hash[(size_t)c] = h;
-                b_len[(size_t)c] = key_is_error(k, L) ? (int16_t)-1 : (int16_t)key_len(k, L);
+                b_len[(size_t)c] = key_is_error(k, L) ? (int16_t)-1 : (int16_t)key_total(k, L);
                 b_own[(size_t)c] = (uint8_t)owner(h);
             }
         });
@@ -693,7 +542,6 @@ struct Engine {
         const int64_t t4 = now_ns();
         ph_ns[2] += t4 - t3;
         // 5. commit
-        const int64_t n0 = n_set;
         keys.resize((size_t)n * kw);
         parent.resize((size_t)n);
         action.resize((size_t)n);
@@ -731,8 +579,7 @@ struct Engine {
         });
         ph_ns[5] += now_ns() - t6;
         n_set = n;
-        (void)n0;
-        // bookkeeping as visit() leaves it
+        // bookkeeping as replay_children() leaves it
         const int64_t visited = stop + 1;  // parents qh .. qh + stop popped (acx_search_popped: ids 0 .. st_pops - 1)
         st_pops += visited;
         last_popped = qh + stop;
@@ -749,7 +596,6 @@ struct Engine {
             const int64_t g = succ / ACT;
             found_parent = qh + g;
             found_action = (int)(succ % ACT);
-            found_len = 2;
             found_explored = qh + g + 1;  // n_set - (len(queue) - head) with every node queued once
             std::memcpy(found_key, ck + (size_t)succ * kw, sizeof(uint64_t) * kw);
         } else if (budget) {
@@ -792,28 +638,6 @@ struct Engine {
         }
         return status;
     }
-
-    // path of node `id` as (action, total) pairs from the root (root = (-1, total))
-    int64_t path(int64_t id, int32_t* acts, int32_t* lens, int64_t cap, bool append_found) const {
-        std::vector<int64_t> chain;
-        for (int64_t v = id; v >= 0; v = parent[v]) chain.push_back(v);
-        int64_t n = 0;
-        for (auto it = chain.rbegin(); it != chain.rend(); ++it) {
-            if (n < cap) {
-                acts[n] = action[*it];
-                lens[n] = total[*it];
-            }
-            ++n;
-        }
-        if (append_found) {
-            if (n < cap) {
-                acts[n] = found_action >= 0 ? found_action : last_action;
-                lens[n] = found_action >= 0 ? found_len : last_len;
-            }
-            ++n;
-        }
-        return n;
-    }
 };
 
 }  // namespace
@@ -841,19 +665,14 @@ int32_t acx_search_feed(void* h, const uint64_t* child_keys, int64_t count) {
 // the search
 int32_t acx_search_status(void* h, int32_t* budget_hit, int32_t* min_length, int64_t* n_nodes) {
     Engine* e = static_cast<Engine*>(h);
-    if (budget_hit) *budget_hit = e->budget_hit;
-    if (min_length) *min_length = e->min_length;
-    if (n_nodes) *n_nodes = e->n_set;
-    return e->status;
+    return read_status(*e, e->n_set, budget_hit, min_length, n_nodes);
 }
 
 // success: path of the found child; failure (greedy): path of the last popped node plus its
 // last child (greedy.py:121).  Returns the number of (action, total) entries.
 int64_t acx_search_path(void* h, int32_t* actions, int32_t* totals, int64_t cap) {
     Engine* e = static_cast<Engine*>(h);
-    if (e->status == 1) return e->path(e->found_parent, actions, totals, cap, true);
-    if (e->last_popped < 0) return 0;
-    return e->path(e->last_popped, actions, totals, cap, true);
+    return read_path(*e, e->parent.data(), e->action.data(), e->total.data(), actions, totals, cap);
 }
 
 // BFS batch phases (tools/host_bfs_bench.cpp; not in the public header): ns in 2 (scan), 3
@@ -882,40 +701,26 @@ int64_t acx_search_popped(void* h, int64_t* ids, int64_t cap) {
         for (int64_t i = 0; ids && i < e->st_pops && i < cap; ++i) ids[i] = i;
         return e->st_pops;
     }
-    const int64_t n = (int64_t)e->popped.size();
-    for (int64_t i = 0; ids && i < n && i < cap; ++i) ids[i] = e->popped[(size_t)i];
-    return n;
+    return read_array(e->popped.data(), (int64_t)e->popped.size(), ids, cap);
 }
 
 // the new minimum totals in the order found (the verbose "New minimal length found" lines)
 int64_t acx_search_min_trace(void* h, int32_t* out, int64_t cap) {
     Engine* e = static_cast<Engine*>(h);
-    const int64_t n = (int64_t)e->trace.size();
-    for (int64_t i = 0; out && i < n && i < cap; ++i) out[i] = e->trace[(size_t)i];
-    return n;
+    return read_array(e->trace.data(), (int64_t)e->trace.size(), out, cap);
 }
 
 // after a success: the first letters of both relators of the found child (each of length 1) and
 // len(tree_nodes) - len(to_explore) at that moment (greedy.py:92-95); returns 1, else 0
 int32_t acx_search_found(void* h, int32_t* first_letters, int64_t* explored) {
     Engine* e = static_cast<Engine*>(h);
-    if (e->status != 1) return 0;
-    static const int32_t letter[4] = {1, -1, 2, -2};
-    const int bit1 = 2 * e->L;
-    if (first_letters) {
-        first_letters[0] = letter[e->found_key[0] & 3u];
-        first_letters[1] = letter[(e->found_key[bit1 >> 6] >> (bit1 & 63)) & 3u];
-    }
-    if (explored) *explored = e->found_explored;
-    return 1;
+    return read_found(*e, e->L, first_letters, explored);
 }
 
 // copy the packed keys of the first min(cap, n_nodes) discovered nodes (discovery order)
 int64_t acx_search_node_keys(void* h, uint64_t* out, int64_t cap) {
     Engine* e = static_cast<Engine*>(h);
-    const int64_t n = e->n_set < cap ? e->n_set : cap;
-    if (out && n > 0) std::memcpy(out, e->keys.data(), sizeof(uint64_t) * (size_t)n * e->kw);
-    return e->n_set;
+    return read_array(e->keys.data(), e->n_set, out, cap, e->kw);
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "acx.h"
+#include "../../ac-solver-caltech_amd/csrc/acx_key.h"
 
 extern "C" {
 int32_t acx_key_words(int32_t L) { return (4 * L + 16 + 63) / 64; }
@@ -21,40 +22,20 @@ void acx_oracle_expand12(const int32_t* parents, int64_t N, int32_t L, int32_t c
                          int32_t* lengths, uint8_t* err);
 }
 
-// tests/test_cpu_host.py _pack_key / _oracle_keys: 2-bit codes r0 then r1, then the 8-bit
-// letter counts at bit 4L; a child whose move raised gets both length bytes 0xFF
+// the key of a child (acx_key.h pack_key); the harness plays the GPU here, so a child whose move
+// raised gets the error sentinel from the harness's own writer: all 16 length bits at bit 4L set
 static void pack(const int32_t* s, int L, uint64_t* k, int kw, bool error) {
-    for (int i = 0; i < kw; ++i) k[i] = 0;
-    for (int h = 0; h < 2; ++h) {
-        int n = 0;
-        for (int i = 0; i < L; ++i) {
-            const int v = s[h * L + i];
-            if (!v) continue;
-            ++n;
-            const uint64_t c = v == 1 ? 0 : v == -1 ? 1 : v == 2 ? 2 : 3;
-            const int bit = 2 * (h * L + i);
-            k[bit >> 6] |= c << (bit & 63);
-        }
-        const uint64_t b = error ? 0xffu : (uint64_t)n;
-        for (int j = 0; j < 8; ++j) {
-            const int bit = 4 * L + 8 * h + j;
-            k[bit >> 6] |= ((b >> j) & 1u) << (bit & 63);
-        }
+    acx::pack_key(s, L, kw, k);
+    for (int j = 0; error && j < 16; ++j) {
+        const int bit = 4 * L + j;
+        k[bit >> 6] |= 1ull << (bit & 63);
     }
 }
 
 static void unpack(const uint64_t* k, int L, int32_t* s) {
-    static const int32_t let[4] = {1, -1, 2, -2};
     for (int h = 0; h < 2; ++h) {
-        int n = 0;
-        for (int j = 0; j < 8; ++j) {
-            const int bit = 4 * L + 8 * h + j;
-            n |= (int)((k[bit >> 6] >> (bit & 63)) & 1u) << j;
-        }
-        for (int i = 0; i < L; ++i) {
-            const int bit = 2 * (h * L + i);
-            s[h * L + i] = i < n ? let[(k[bit >> 6] >> (bit & 63)) & 3u] : 0;
-        }
+        const int n = acx::key_len(k, L, h);
+        for (int i = 0; i < L; ++i) s[h * L + i] = i < n ? acx::key_letter(acx::key_code_at(k, L, h, i)) : 0;
     }
 }
 
