@@ -1,7 +1,9 @@
 // CPU check of the bit-plane word algebra (ac-solver-caltech_amd/csrc/acx_planes.h, compiled for
 // the host) against the C oracle (oracle/acx_oracle.c, pinned to the reference's fixtures):
 // ac_move on arbitrary states (unreduced, empty relators, bad move ids), ac_move_clean on clean
-// states, random walks of clean moves, and the int8 -> plane pack conversion.  Test
+// states, random walks of clean moves, the int8 -> plane pack conversion, and rows with a junction
+// cancellation and a cyclic peel of a chosen depth next to a word boundary (planted(): uniform random
+// letters reach a depth d with probability 3^-d, so never the second plane word).  Test
 // infrastructure, built and run by tests/test_planes_host.py.
 //   planes_check <cases> <seed>   -> prints "ok <n>" or the first mismatch, exit status 0 / 1
 #include <stdint.h>
@@ -198,20 +200,133 @@ static int run(int L, int cases, std::mt19937_64& rng) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// planted cancellations: r_i = p A u, r_j^sign = u^-1 B p^-1 with |u| = k (the junction depth)
+// and |p| = m (the cyclic peel's depth) from {0, 1, 16j - 1, 16j, 16j + 1, L - 2}, the tails
+// (|A|, |B|) from (1,1), (0,2), (2,0), (3,5); the product p A B p^-1 is 2m + |A| + |B| letters
+// before the peel (the length gate's operand) and A B after it.  tests/planted_rows.py is the same
+// construction for the GPU tests.
+// ---------------------------------------------------------------------------------------------
+typedef std::vector<int32_t> W;
+
+static void rword(std::mt19937_64& rng, int n, int after, W& out) {  // n more letters, freely reduced after `after`
+    const int letters[4] = {1, 2, -1, -2};
+    for (int k = 0; k < n; ++k) {
+        int c;
+        do c = letters[rng() % 4]; while (c == -after);
+        out.push_back(after = c);
+    }
+}
+static W winv(const W& w) {
+    W r(w.rbegin(), w.rend());
+    for (auto& x : r) x = -x;
+    return r;
+}
+static bool reduced(const W& w, bool cyc) {
+    for (size_t k = 0; k + 1 < w.size(); ++k)
+        if (w[k] == -w[k + 1]) return false;
+    return !cyc || w.size() < 2 || w.front() != -w.back();
+}
+static W cat(std::initializer_list<const W*> parts) {
+    W r;
+    for (const W* q : parts) r.insert(r.end(), q->begin(), q->end());
+    return r;
+}
+
+// the three moves on one row against the oracle: general, clean if the row is clean, pair if PW = 1
+template <int PW>
+static int check_row(const char* what, const int32_t* in, int L, int a, int cyc) {
+    std::vector<int32_t> out(2 * L), got(2 * L);
+    int32_t lens[2];
+    const int ew = acx_oracle_move(in, L, a, cyc, out.data(), lens);
+    const int32_t* want = ew ? in : out.data();
+    const PlaneRegs<PW> p0 = to_planes<PW>(in, L);
+    PlaneRegs<PW> p = p0;
+    const int eg = pl::ac_move<PW>(p.w0, p.n0, p.w1, p.n1, a, L, cyc != 0);
+    from_planes<PW>(p, L, got.data());
+    if (ew != eg || memcmp(want, got.data(), 8 * L) != 0) return fail(what, L, a, cyc, in, want, got.data(), ew, eg);
+    if (!pl::is_clean<PW>(p0.w0, p0.n0, p0.w1, p0.n1, cyc != 0)) return 0;
+    p = p0;
+    const int ec = pl::ac_move_clean<PW>(p.w0, p.n0, p.w1, p.n1, a, L, cyc != 0);
+    from_planes<PW>(p, L, got.data());
+    if (ew != ec || memcmp(want, got.data(), 8 * L) != 0) return fail("planted clean", L, a, cyc, in, want, got.data(), ew, ec);
+    if constexpr (PW == 1) {
+        PlaneRegs<1> r;
+        int e3;
+        if (!pair_clean(p0, a, L, cyc != 0, r, e3)) return fail("planted pair contract", L, a, cyc, in, in, in, 0, -1);
+        from_planes<1>(r, L, got.data());
+        if (ew != e3 || memcmp(want, got.data(), 8 * L) != 0) return fail("planted pair", L, a, cyc, in, want, got.data(), ew, e3);
+    }
+    return 0;
+}
+
+template <int PW>
+static int planted(int L, std::mt19937_64& rng, long& rows) {
+    std::vector<int> D = {0, 1, L - 2};
+    for (int j = 1; j <= 7; ++j)
+        for (int d = 16 * j - 1; d <= 16 * j + 1; ++d) D.push_back(d);
+    const int tails[4][2] = {{1, 1}, {0, 2}, {2, 0}, {3, 5}};
+    std::vector<int32_t> in(2 * L);
+    for (int k : D) for (int m : D) for (const auto& t : tails) {
+        const int ta = t[0], tb = t[1];
+        if (k < 0 || m < 0 || k + m + ta > L || k + m + tb > L || k + m + ta < 1 || k + m + tb < 1) continue;
+        if (k < 15 && m < 15 && L > 16) continue;
+        W ri, w;
+        for (int attempt = 0; attempt < 10000; ++attempt) {
+            W p, A, u, B;
+            rword(rng, m, 0, p);
+            rword(rng, ta, p.empty() ? 0 : p.back(), A);
+            rword(rng, k, !A.empty() ? A.back() : !p.empty() ? p.back() : 0, u);
+            rword(rng, tb, u.empty() ? 0 : -u.front(), B);
+            const W ip = winv(p), iu = winv(u);
+            ri = cat({&p, &A, &u});
+            w = cat({&iu, &B, &ip});
+            if (reduced(ri, true) && reduced(w, true) && reduced(cat({&p, &A, &B, &ip}), false) && reduced(cat({&A, &B}), true)) break;
+        }
+        for (int a = 0; a < 4; ++a) {
+            const int i = (a + 1) & 1;
+            const W rj = (a == 1 || a == 2) ? winv(w) : w;
+            for (int twin = 0; twin < 2; ++twin) {
+                W rel[2];
+                rel[i] = ri;
+                rel[1 - i] = rj;
+                if (twin) {  // one cancelling pair inside r_i, between p and A (away from the junction): not clean
+                    if ((int)ri.size() + 2 > L) continue;
+                    const int prev = m ? ri[m - 1] : 0, next = m < (int)ri.size() ? ri[m] : 0;
+                    int x = 1;
+                    for (int c : {1, 2, -1, -2}) if (c != -prev && c != next) x = c;
+                    rel[i].insert(rel[i].begin() + m, {x, -x});
+                }
+                std::fill(in.begin(), in.end(), 0);
+                for (int h = 0; h < 2; ++h) std::copy(rel[h].begin(), rel[h].end(), in.begin() + h * L);
+                for (int cyc = 0; cyc < 2; ++cyc) {
+                    if (check_row<PW>(twin ? "planted twin" : "planted", in.data(), L, a, cyc)) return 1;
+                    ++rows;
+                }
+                // the same row under the other eleven ids (the conjugations of a full-length relator)
+                for (int b = 0; b < 12; ++b)
+                    if (b != a && check_row<PW>("planted, other id", in.data(), L, b, (int)(rows & 1))) return 1;
+            }
+        }
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const int cases = argc > 1 ? atoi(argv[1]) : 20000;
     std::mt19937_64 rng(argc > 2 ? strtoull(argv[2], nullptr, 10) : 1);
     int total = 0;
+    long rows = 0;
     const int Ls1[] = {1, 2, 3, 5, 7, 8, 13, 16, 17, 18, 31, 32, 33, 36, 47, 48, 63, 64};
     for (int L : Ls1) {
-        if (run<1>(L, cases, rng)) return 1;
+        if (run<1>(L, cases, rng) || planted<1>(L, rng, rows)) return 1;
         total += cases;
     }
     const int Ls2[] = {65, 80, 100, 127, 128};
     for (int L : Ls2) {
-        if (run<2>(L, cases, rng)) return 1;
+        if (run<2>(L, cases, rng) || planted<2>(L, rng, rows)) return 1;
         total += cases;
     }
-    printf("ok %d\n", total);
+    printf("ok %d random, %ld planted\n", total, rows);
     return 0;
 }

@@ -2,7 +2,9 @@
 built for the host) against the C oracle (oracle/acx_oracle.c, itself pinned to the reference's
 fixtures by tests/test_oracle.py): ac_move on arbitrary states incl. unreduced words, empty
 relators and bad move ids, ac_move_clean on clean states, 200-step walks of clean cyclic moves,
-strict triviality and the int8 -> plane pack, at L = 1..64 (one plane word) and 65..128 (two)."""
+strict triviality, the int8 -> plane pack, and rows with a junction cancellation and a cyclic peel
+planted at every word-boundary depth (general, clean and two-lane pair move), at L = 1..64 (one
+plane word) and 65..128 (two)."""
 import os
 import subprocess
 
