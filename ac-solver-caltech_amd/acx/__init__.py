@@ -2,13 +2,15 @@
 path of Avi161/AC-Solver-Caltech), HIP kernels behind the C-ABI in include/acx.h.
 
 Public names mirror the reference's ac_solver/__init__.py:1-6 (ACEnv, ACEnvConfig, bfs,
-greedy_search); VecACEnv and acx.ops are the batched device API.
+greedy_search); VecACEnv and acx.ops are the batched device API, bfs_many is bfs over a batch
+of presentations in one launch.
 """
 
 from .envs.ac_env import ACEnv, ACEnvConfig, VecACEnv
 from .envs.ac_moves import ACMove
 from .search.breadth_first import bfs
+from .search._batch_bfs import bfs_many
 from .search.greedy import greedy_search
 from . import data  # noqa: F401
 
-__all__ = ["ACEnv", "ACEnvConfig", "VecACEnv", "ACMove", "bfs", "greedy_search"]
+__all__ = ["ACEnv", "ACEnvConfig", "VecACEnv", "ACMove", "bfs", "bfs_many", "greedy_search"]

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("ACX_LIB", os.path.join(HERE, "libacx.so"))
 
 OK, E_ARG, E_LAUNCH = 0, -1, -2
 BFS_EXHAUSTED, BFS_FOUND, BFS_BUDGET, BFS_MOVE_ERROR = 0, 1, 2, 3
+MBFS_DOMAIN, MBFS_OVERFLOW = -3, -4
 ERR_NONE, ERR_INVALID, ERR_EMPTY_CONJ, ERR_DOMAIN, ERR_ACTION, ERR_PAD = 0, 1, 2, 3, 4, 9
 MAX_L = 128
 
@@ -87,6 +88,12 @@ SIGNATURES = {
     "acx_bfs_destroy": ([_P], None),
     "acx_bfs_node_keys": ([_P, _P, _I64, _P], ctypes.c_int64),
     "acx_bfs_min_trace": ([_P, _P, _I64], ctypes.c_int64),
+    # batched BFS, one workgroup per search (ac-solver-caltech_amd/csrc/acx_mbfs.hip)
+    "acx_mbfs_bytes": ([_I32, _I64], ctypes.c_int64),
+    "acx_mbfs_create": ([_I32, _I64, _I64, _I32], ctypes.c_void_p),
+    "acx_mbfs_run": ([_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    "acx_mbfs_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
+    "acx_mbfs_destroy": ([_P], None),
     # owner-partitioned multi-GPU BFS (ac-solver-caltech_amd/csrc/acx_sbfs.hip)
     "acx_sbfs_create": ([_I32, _I64, _I64, _I32, _I32, _I32], ctypes.c_void_p),
     "acx_sbfs_destroy": ([_P], None),

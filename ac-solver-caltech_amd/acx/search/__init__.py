@@ -1,4 +1,5 @@
+from ._batch_bfs import bfs_many
 from .breadth_first import bfs
 from .greedy import greedy_search
 
-__all__ = ["bfs", "greedy_search"]
+__all__ = ["bfs", "bfs_many", "greedy_search"]

@@ -35,11 +35,13 @@ def _handle(lib, dev: torch.device, L: int, cyclical: bool, chunk: int, max_node
 
 
 def release_workspaces() -> None:
-    """Free the cached device workspaces."""
+    """Free the cached device workspaces (the batched BFS's too)."""
     lib = _lib.load()
     for ptr, _ in _HANDLES.values():
         lib.acx_bfs_destroy(ptr)
     _HANDLES.clear()
+    from . import _batch_bfs
+    _batch_bfs.release_workspaces()
 
 
 def device_bfs(presentation, max_nodes_to_explore=10000, verbose=False, cyclically_reduce_after_moves=False,

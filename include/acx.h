@@ -398,6 +398,47 @@ int64_t acx_bfs_node_keys(void* h, uint64_t* out, int64_t cap, void* stream);
 int64_t acx_bfs_min_trace(void* h, int32_t* out, int64_t cap);
 
 /*
+ * Breadth-first search over a batch of presentations in one launch (csrc/acx_mbfs.hip): one
+ * workgroup owns one search from root to verdict, its node store and visited set a private slice
+ * of the handle's workspace.  Every search gives the result of bfs on its own presentation,
+ * ac_solver/search/breadth_first.py:15-97, the same as acx_bfs_run.
+ *   acx_mbfs_bytes   (breadth_first.py:15-97) workspace bytes per search for budgets up to
+ *                    max_nodes_each = B at max_relator_length L, kw = acx_key_words(L):
+ *                      8 kw B + 4 B + 64 ceil((B + 779) / 4) + 32 [+ 6144 kw when L > 64]
+ *                    (node keys, parent/action words, a visited set at load <= 1/2 of
+ *                    B + 11 + 768 entries, the verdict record, the round's child keys where they
+ *                    do not stay in LDS); ACX_E_ARG for L outside [1, ACX_MAX_L] or B outside
+ *                    [1, 2^24].
+ *   acx_mbfs_create  (breadth_first.py:15-97) allocates n_searches times that on the current
+ *                    device; NULL on bad arguments or when the workspace does not fit.
+ *   acx_mbfs_run     (breadth_first.py:15-97) searches n <= n_searches presentations: `states`
+ *                    DEVICE (n, 2L) int32, `budgets` DEVICE (n) int64 (a budget < 1 behaves as 1,
+ *                    as in acx_bfs_run), outputs DEVICE arrays of n: status (an ACX_BFS_* value,
+ *                    ACX_MBFS_DOMAIN for a state outside the packed domain or with an empty
+ *                    relator -- it is not searched -- or ACX_MBFS_OVERFLOW), nodes
+ *                    (len(tree_nodes) at the ending event: what the reference's "Exiting
+ *                    search" line prints on ACX_BFS_BUDGET), parents expanded, min_length (the
+ *                    minimum child total up to the ending event), path_len (entries of the
+ *                    reference's path on ACX_BFS_FOUND, else 0).  Asynchronous on `stream`.  A
+ *                    handle is reusable: a later run never sees an earlier run's visited sets.
+ *   acx_mbfs_paths   (breadth_first.py:85,89) after a run, on the same stream: for every search
+ *                    with ACX_BFS_FOUND the reference's path [(-1, total0), (action, total), ...]
+ *                    in CSR form -- search q's path_len[q] entries start at offsets[q] (DEVICE
+ *                    (n) int64, the exclusive prefix sum of path_len) in `actions` / `totals`
+ *                    (DEVICE int32, `cap` entries each; a path that would pass cap is skipped).
+ *   acx_mbfs_destroy (breadth_first.py:15-97) frees the workspace.
+ */
+#define ACX_MBFS_DOMAIN (-3)   /* per-search status: state outside the packed domain, not searched */
+#define ACX_MBFS_OVERFLOW (-4) /* per-search status: budget above max_nodes_each, or a full table */
+int64_t acx_mbfs_bytes(int32_t L, int64_t max_nodes_each);
+void* acx_mbfs_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t cyclical);
+int acx_mbfs_run(void* h, const int32_t* states, const int64_t* budgets, int64_t n, int32_t* status, int64_t* nodes,
+                 int64_t* parents, int32_t* min_length, int64_t* path_len, void* stream);
+int acx_mbfs_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
+                   void* stream);
+void acx_mbfs_destroy(void* h);
+
+/*
  * Breadth-first search with the node store and the visited set partitioned over G GPUs by key
  * owner (one process per GPU).  Same results as acx_bfs_run / the
  * reference bfs (breadth_first.py:15-97).  The caller runs the same chunk loop on every rank
