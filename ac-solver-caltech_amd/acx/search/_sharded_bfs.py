@@ -117,6 +117,20 @@ def local_capacity(max_nodes: int, world: int) -> int:
     return min(n, (n + world - 1) // world * 5 // 4 + 4096)
 
 
+def _chunk_verdict(succ_seq, err_seq, cut_p, P):
+    """(kind, children the reference looked at, last parent it counts) for a chunk of P parents:
+    csrc/acx_bfs_verdict.h's chunk_verdict (same inputs, NONE where there is none; kind is a
+    _lib.BFS_* status or 0: the search goes on), held to the same table by
+    tests/test_bfs_verdict_host.py."""
+    if err_seq != NONE and err_seq <= succ_seq and err_seq // 12 <= cut_p:
+        return _lib.BFS_MOVE_ERROR, err_seq, err_seq // 12
+    if succ_seq != NONE and succ_seq // 12 <= cut_p:
+        return _lib.BFS_FOUND, succ_seq + 1, succ_seq // 12
+    if cut_p != NONE:
+        return _lib.BFS_BUDGET, 12 * (cut_p + 1), cut_p
+    return 0, 12 * P, P - 1
+
+
 TRACE_CAP = 512  # (seq, total) records per rank per chunk (acx_sbfs_trace; <= 2L + 1 in practice)
 
 
@@ -247,34 +261,21 @@ def sharded_bfs(presentation, max_nodes_to_explore=10000, verbose=False, cyclica
                 if st_rows[1]:
                     raise _lib.ACXError("sharded bfs: a rank's node store or hash table is full")
             total_new, cut_p, nodes_at_cut = int(com_out[0]), int(com_out[1]), int(com_out[2])
-            cut = cut_p if cut_p >= 0 else None
-            err_p = err_seq // 12 if err_seq != NONE else None
-            suc_p = succ_seq // 12 if succ_seq != NONE else None
-            err_first = err_p is not None and err_seq < succ_seq and (cut is None or err_p <= cut)
-            succ_first = not err_first and suc_p is not None and (cut is None or suc_p <= cut)
+            kind, end_seq, last = _chunk_verdict(succ_seq, err_seq, cut_p if cut_p >= 0 else NONE, P)
             if verbose and chunk_min < trace_min:
-                # the chunk's children the reference visits: up to (not incl.) the raising one, incl.
-                # the successful one, through the cut parent, or all of them
-                end_seq = (err_seq if err_first else succ_seq + 1 if succ_first else
-                           12 * (cut + 1) if cut is not None else 12 * P)
                 trace_min = _trace_chunk(lib, h, comm, trace_buf, trace_min, end_seq, stream, ok, agree,
                                          trace_lines)
-            if err_first or succ_first or cut is not None:
-                last = err_p if err_first else suc_p if succ_first else cut
-                if succ_first:
+            if kind:
+                if kind == _lib.BFS_FOUND:
                     min_len = 2
+                    succ_node, succ_act = head + last, succ_seq % 12
                 else:
                     m = comm.min_rows([lib.acx_sbfs_min_len(h, last, stream)])[0]
                     min_len = min(min_len, int(m))
+                    if kind == _lib.BFS_BUDGET:
+                        n_nodes = nodes_at_cut
                 parents += last + 1
-                if err_first:
-                    status = _lib.BFS_MOVE_ERROR
-                elif succ_first:
-                    status = _lib.BFS_FOUND
-                    succ_node, succ_act = head + suc_p, succ_seq % 12
-                else:
-                    status = _lib.BFS_BUDGET
-                    n_nodes = nodes_at_cut
+                status = kind
                 break
             min_len = min(min_len, chunk_min)
             parents += P

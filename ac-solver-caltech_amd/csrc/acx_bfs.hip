@@ -21,9 +21,8 @@
 // parents (one wave), action-major inside a tile, so a wave writes each action's 64 keys as
 // one contiguous run.  A node is named by its code (1 = root, s + 2 = child s); the FIFO queue
 // holds codes, and a node's parent is queue[(code - 2) / 12] -- no compaction copy of keys, no
-// parent / move arrays.  The visited set maps a state to the code of its first occurrence:
-// entry = code << 24 | 24-bit fingerprint, buckets of 8 entries (one 64-B line per probe).
-// Within a chunk the first occurrence wins by atomicMin on the entry (codes order as the
+// parent / move arrays.  The visited set (acx_visited.h: format, insert protocol) maps a state to
+// the code of its first occurrence.  Within a chunk the first occurrence wins (codes order as the
 // reference does); the child whose entry is replaced is told so by the replacing child
 // (`lost`), so survivors are known without re-reading the table.
 //
@@ -32,14 +31,14 @@
 //                         actions 3w..3w+2), child keys staged through LDS and written
 //                         coalesced; first success / move-error seq, per-parent min child total;
 //   2. bfs_insert_kernel  lane per child (up to the search's last child): probe / claim /
-//                         join the state's table entry;
+//                         join the state's table entry (visited::insert);
 //   3. bfs_count_kernel   wave per tile: survivors per tile;
 //   4. bfs_scan_kernel    exclusive scan of the tile counts;
 //   5. bfs_commit_kernel  wave per tile: survivors' codes appended to the queue in (parent,
 //                         action) order (LDS-staged, coalesced), the node-budget cut;
-//   6. bfs_close_kernel   one block: the reference's decision for the chunk, the min_length
-//                         trace, the next chunk's parameters (Live, on the device) and a copy
-//                         of the state in pinned host memory.
+//   6. bfs_close_kernel   one block: the reference's decision for the chunk (chunk_verdict,
+//                         acx_bfs_verdict.h), the min_length trace, the next chunk's parameters
+//                         (Live, on the device) and a copy of the state in pinned host memory.
 // The host never sits between chunks: it keeps one chunk enqueued beyond the one whose outcome
 // it is reading (grids sized for an upper bound, parameters read from Live), so a chunk's
 // kernels follow the previous chunk's back to back (round 3: 10^7 nodes had 8 host round trips
@@ -61,27 +60,17 @@
 #include "acx_moves.h"
 
 #include "acx_bfs_common.h"
-
-// visited-set sizing: the table has >= 100/ACX_BFS_TABLE_LOAD_PCT entries per bound entry (every
-// node plus every claimed chunk entry), power of two; see acx_bfs_create
-#ifndef ACX_BFS_TABLE_LOAD_PCT
-#define ACX_BFS_TABLE_LOAD_PCT 50
-#endif
+#include "acx_bfs_verdict.h"
+#include "acx_visited.h"
 
 namespace acx {
 namespace bfs {
 
 constexpr int TILE = 64;                // parents per tile (one wave)
 constexpr int TILE_CH = 12 * TILE;      // children per tile
-constexpr int BUCKET = 8;               // table entries per bucket (64 B)
 constexpr int TRACE_CAP = 1024;         // new-minimum records per trace walk (<= 2L + 1 ever)
-constexpr uint32_t FP_MASK = 0xffffffu;
-// 8-entry table: entry = epoch << 58 | code << 24 | fp; codes < 12 (2^30 + 12) + 14 < 2^34.  An
-// entry of another epoch (an earlier search on this workspace) is an empty slot, so a search
-// does not clear the table (it did: a 512 MB memset per 10^7-node search); the table is
-// cleared only when the 6-bit epoch wraps.
-constexpr int EP_SHIFT = 58;
-constexpr uint64_t CODE_MASK = (1ull << 34) - 1;
+using visited::BUCKET;
+// codes < 12 (2^30 + 12) + 14 < 2^34 = visited::CODE_MASK + 1
 
 // store index (in keys) of the node with code c
 __host__ __device__ __forceinline__ int64_t store_index(uint64_t c) {
@@ -140,8 +129,7 @@ struct Args {
     int64_t need;      // max_nodes - n_before
     int64_t qcap;
     int P, L, kw, cyc, ntiles;
-    int kt;            // key-in-table layout (bfs_insert_kt_kernel)
-    uint64_t ep;       // this search's epoch << EP_SHIFT (8-entry table)
+    uint64_t ep;       // this search's epoch, shifted (visited::next_epoch)
 };
 
 // this chunk's parameters from the device-side state; false once the search has ended (the
@@ -191,9 +179,8 @@ __global__ __launch_bounds__(TPB, NW <= 4 ? 8 : 4) void bfs_expand_kernel(Args a
     for (int j = 0; j < APW; ++j) {
         const int act = wid * APW + j;
         if (active) {
-            PresRegs<NW> q = pr;
-            const int e = clean ? ac_move_clean<NW>(q.w0, q.n0, q.w1, q.n1, act, a.L, a.cyc != 0)
-                                : ac_move<NW>(q.w0, q.n0, q.w1, q.n1, act, a.L, a.cyc != 0);
+            PresRegs<NW> q;
+            const int e = child_of<NW>(pr, clean, act, a.L, a.cyc != 0, q);
             const uint32_t s = p * 12u + (uint32_t)act;
             if (e != ACX_ERR_NONE) {
                 err = min(err, s);
@@ -245,106 +232,27 @@ __device__ __forceinline__ int64_t local_pos(const Args& a, uint64_t c) {
     return (int64_t)(((int64_t)(g >> 6) - a.tile0) * TILE_CH + act * TILE + (g & 63));
 }
 
-// Key-in-table layout (L <= KT_MAX_L: the 4L + 16 key bits fit 3 x 63): an entry is 4 words,
-// [code << 24 | fp, g0, g1, g2], two entries per 64-B bucket; g_j = (bits [63j, 63j + 63) of the
-// key) << 1 | 1.  The claimer CASes the first word, then stores g0..g2, so a reader sees each g_j
-// either as written (guard bit 1: the entry's state's key bits, exactly) or still 0: an entry
-// whose three guards are set decides equality from the bucket line alone; otherwise the state's
-// key is read from the store, as in the 8-entry layout.
-constexpr int KT_MAX_L = 43;
-constexpr int KT_ENT = 4;  // words per entry
-__host__ __device__ __forceinline__ void kt_guarded(const uint64_t* k, int kw, uint64_t (&g)[3]) {
-    const uint64_t k0 = k[0], k1 = kw > 1 ? k[1] : 0ull, k2 = kw > 2 ? k[2] : 0ull;
-    const uint64_t M = (1ull << 63) - 1;
-    g[0] = ((k0 & M) << 1) | 1ull;
-    g[1] = ((((k0 >> 63) | (k1 << 1)) & M) << 1) | 1ull;
-    g[2] = (((k1 >> 62) | (k2 << 2)) << 1) | 1ull;
-}
-
-// (2') key-in-table insert: a duplicate of a committed node costs one random line (its bucket)
-template <int KWM>
-__global__ __launch_bounds__(TPB, 8) void bfs_insert_kt_kernel(Args a) {
-    if (!chunk_args(a)) return;
-    const int64_t c = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (c >= (int64_t)a.ntiles * TILE_CH) return;
-    const int t = (int)(c / TILE_CH);
-    const int r = (int)(c - (int64_t)t * TILE_CH);
-    const int act = r / TILE, lane = r - act * TILE;
-    const int64_t g = (a.tile0 + t) * TILE + lane;
-    uint8_t res = 0;
-    if (g >= a.head && g < a.head + a.P) {
-        const uint32_t s = (uint32_t)(g - a.head) * 12u + (uint32_t)act;
-        const uint32_t end = min(a.ctl->succ, a.ctl->err);
-        if (s < end) {
-            const int kw = a.kw;
-            const uint64_t code = (uint64_t)g * 12 + act + 2;
-            const Key<KWM> key = kload<KWM>(a.store + (1 + (a.tile0 + t) * TILE_CH + r) * kw, kw);
-            const uint64_t h = khash<KWM>(key, kw);
-            const uint32_t fp = (uint32_t)(h >> 40);
-            const uint64_t my = (code << 24) | fp;
-            uint64_t gd[3];
-            kt_guarded(key.w, kw, gd);
-            uint64_t b = h & a.bmask;
-            for (uint64_t it = 0;; ++it) {
-                if (it > a.bmask) {
-                    atomicOr(&a.ctl->overflow, 1u);
-                    break;
-                }
-                uint64_t* bk = a.table + b * BUCKET;
-                uint64_t e[BUCKET];
+// the visited set's buckets: a power of two of them, the first by the hash's low bits.  A bucket
+// line is read with plain 16-byte loads: node codes are permanent and an entry only goes empty ->
+// one state's code -> a smaller code of the same state, so a stale read is harmless (a stale
+// empty is corrected by the CAS, a stale entry names the same state)
+struct Buckets {
+    using Index = uint64_t;
+    uint64_t* table;
+    uint64_t bmask;
+    __device__ __forceinline__ Index buckets() const { return bmask + 1; }
+    __device__ __forceinline__ Index first(uint64_t h) const { return h & bmask; }
+    __device__ __forceinline__ Index next(Index b) const { return (b + 1) & bmask; }
+    __device__ __forceinline__ uint64_t* bucket(Index b) const { return table + b * BUCKET; }
+    __device__ __forceinline__ void load(const uint64_t* bk, uint64_t (&e)[BUCKET]) const {
 #pragma unroll
-                for (int j = 0; j < BUCKET; j += 2) {
-                    const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(bk + j);
-                    e[j] = v.x;
-                    e[j + 1] = v.y;
-                }
-                int done = 0;  // 1 seen / lost, 2 holds the entry
-#pragma unroll
-                for (int j = 0; j < BUCKET / KT_ENT && !done; ++j) {
-                    uint64_t* ent = bk + KT_ENT * j;
-                    uint64_t v = e[KT_ENT * j];
-                    bool fresh = true;  // e[] holds this entry's words as read with v
-                    if (v == 0) {
-                        const uint64_t old = atomicCAS((unsigned long long*)ent, 0ull, (unsigned long long)my);
-                        if (old == 0) {
-                            ent[1] = gd[0];
-                            ent[2] = gd[1];
-                            ent[3] = gd[2];
-                            done = 2;
-                            break;
-                        }
-                        v = old;
-                        fresh = false;
-                    }
-                    if (((uint32_t)v & FP_MASK) != fp) continue;
-                    const uint64_t e1 = e[KT_ENT * j + 1], e2 = e[KT_ENT * j + 2], e3 = e[KT_ENT * j + 3];
-                    bool eq;
-                    if (fresh && (e1 & e2 & e3 & 1ull)) eq = e1 == gd[0] && e2 == gd[1] && e3 == gd[2];
-                    else eq = keq<KWM>(a.store + store_index(v >> 24) * kw, key, kw);
-                    if (!eq) continue;
-                    const uint64_t vc = v >> 24;
-                    if (vc < code) {
-                        done = 1;
-                        break;
-                    }
-                    const uint64_t old = atomicMin((unsigned long long*)ent, (unsigned long long)my);
-                    if (old < my) {
-                        done = 1;
-                    } else {
-                        a.lost[local_pos(a, old >> 24)] = 1;
-                        done = 2;
-                    }
-                }
-                if (done) {
-                    res = done == 2;
-                    break;
-                }
-                b = (b + 1) & a.bmask;
-            }
+        for (int j = 0; j < BUCKET; j += 2) {
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(bk + j);
+            e[j] = v.x;
+            e[j + 1] = v.y;
         }
     }
-    a.cand[c] = res;
-}
+};
 
 // (2) lane per child: probe the visited set; claim an empty slot or join the state's entry
 template <int KWM>
@@ -364,57 +272,14 @@ __global__ __launch_bounds__(TPB, 8) void bfs_insert_kernel(Args a) {  // 8 wave
             const int kw = a.kw;
             const uint64_t code = (uint64_t)g * 12 + act + 2;
             const Key<KWM> key = kload<KWM>(a.store + (1 + (a.tile0 + t) * TILE_CH + r) * kw, kw);
-            const uint64_t h = khash<KWM>(key, kw);
-            const uint32_t fp = (uint32_t)(h >> 40);
-            const uint64_t my = a.ep | (code << 24) | fp;
-            uint64_t b = h & a.bmask;
-            for (uint64_t it = 0;; ++it) {
-                if (it > a.bmask) {
-                    atomicOr(&a.ctl->overflow, 1u);
-                    break;
-                }
-                uint64_t* bk = a.table + b * BUCKET;
-                uint64_t e[BUCKET];
-#pragma unroll
-                for (int j = 0; j < BUCKET; j += 2) {
-                    const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(bk + j);
-                    e[j] = v.x;
-                    e[j + 1] = v.y;
-                }
-                int done = 0;  // 1 seen / lost, 2 holds the entry
-#pragma unroll
-                for (int j = 0; j < BUCKET && !done; ++j) {
-                    uint64_t v = e[j];
-                    if ((v >> EP_SHIFT) != (a.ep >> EP_SHIFT)) {  // empty in this search
-                        const uint64_t old = atomicCAS((unsigned long long*)(bk + j), (unsigned long long)v,
-                                                       (unsigned long long)my);
-                        if (old == v) {
-                            done = 2;
-                            break;
-                        }
-                        v = old;  // claimed meanwhile: a value of this search
-                    }
-                    if (((uint32_t)v & FP_MASK) != fp) continue;
-                    const uint64_t vc = (v >> 24) & CODE_MASK;
-                    if (!keq<KWM>(a.store + store_index(vc) * kw, key, kw)) continue;
-                    if (vc < code) {  // an earlier occurrence (a node, or an earlier child of the chunk)
-                        done = 1;
-                        break;
-                    }
-                    const uint64_t old = atomicMin((unsigned long long*)(bk + j), (unsigned long long)my);
-                    if (old < my) {
-                        done = 1;
-                    } else {  // replaced a later child of the chunk: it learns it lost
-                        a.lost[local_pos(a, (old >> 24) & CODE_MASK)] = 1;
-                        done = 2;
-                    }
-                }
-                if (done) {
-                    res = done == 2;
-                    break;
-                }
-                b = (b + 1) & a.bmask;
-            }
+            const visited::Outcome ins = visited::insert(
+                Buckets{a.table, a.bmask}, a.ep, code, khash<KWM>(key, kw),
+                [&](uint64_t vc) { return keq<KWM>(a.store + store_index(vc) * kw, key, kw); },
+                [&](uint64_t, uint64_t displaced) {  // a later child of the chunk that held it learns it lost
+                    if (displaced != visited::NO_CODE) a.lost[local_pos(a, displaced)] = 1;
+                });
+            if (ins == visited::FULL) atomicOr(&a.ctl->overflow, 1u);
+            res = ins == visited::HELD;
         }
     }
     a.cand[c] = res;
@@ -444,41 +309,17 @@ __global__ __launch_bounds__(TPB) void bfs_count_kernel(Args a) {
     if (lane == 0) a.tsum[t] = n;
 }
 
-// (4) exclusive scan of the tile counts (one block of 1024 threads)
+// (4) exclusive scan of the tile counts (one block of 1024 threads); the tiles' min child totals
+// into the chunk's
 __global__ __launch_bounds__(1024) void bfs_scan_kernel(Args a) {
     __shared__ uint32_t sh[1024 / WAVE];
     if (!chunk_args(a)) return;
-    const int t = threadIdx.x, lane = t & (WAVE - 1), wid = t / WAVE;
-    const int nb = a.ntiles;
-    const int per = (nb + 1023) / 1024;
-    const int b0 = t * per, b1 = min(nb, b0 + per);
-    uint32_t loc = 0, mn = 0xffffffffu;
-    for (int i = b0; i < b1; ++i) {
-        loc += a.tsum[i];
-        mn = min(mn, a.tmin[i]);
-    }
-    mn = wave_min(mn);
-    if (lane == 0) atomicMin(&a.ctl->min_len, mn);  // 16 per chunk
-    uint32_t x = loc;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, WAVE);
-        if (lane >= o) x += y;
-    }
-    if (lane == WAVE - 1) sh[wid] = x;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-    for (int i = 0; i < 1024 / WAVE; ++i) {
-        off += i < wid ? sh[i] : 0u;
-        tot += sh[i];
-    }
-    uint32_t run = off + x - loc;
-    for (int i = b0; i < b1; ++i) {
-        const uint32_t c = a.tsum[i];
-        a.tsum[i] = run;
-        run += c;
-    }
+    const int t = threadIdx.x;
+    uint32_t mn = 0xffffffffu;
+    const uint32_t tot = scan_array_1024(a.tsum, a.ntiles, sh, [&](int i) { mn = min(mn, a.tmin[i]); });
     if (t == 0) a.ctl->total_new = tot;
+    mn = wave_min(mn);
+    if ((t & (WAVE - 1)) == 0) atomicMin(&a.ctl->min_len, mn);  // 16 per chunk
 }
 
 // (5) append the survivors' codes in (parent, action) order; the node-budget cut
@@ -492,20 +333,14 @@ __global__ __launch_bounds__(TPB) void bfs_commit_kernel(Args a) {
     const bool active = g >= a.head && g < a.head + a.P;
     const uint32_t m = survivors(a, t, lane, true);  // (0 for inactive lanes: cand is 0)
     const uint32_t c = __popc(m);
-    uint32_t x = c;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, WAVE);
-        if (lane >= o) x += y;
-    }
+    const uint32_t x = wave_incl_sum(c, lane);
     const uint32_t excl = x - c;
     const uint32_t wtot = __shfl(x, WAVE - 1, WAVE);
     const int64_t base = (int64_t)a.tsum[t] + excl;  // survivors of the chunk before this parent
     if (active) {
-        // cut = first parent with n_before + (nodes appended through it) >= max_nodes
         const int64_t incl = base + c;
         const int64_t p = g - a.head;
-        if (incl >= a.need && (base < a.need || p == 0)) {
+        if (budget_cut_after(base, incl, a.need, p == 0)) {
             a.ctl->cut_p = (uint32_t)p;
             a.ctl->nodes_at_cut = (uint64_t)(a.n_before + incl);
         }
@@ -523,11 +358,6 @@ __global__ __launch_bounds__(TPB) void bfs_commit_kernel(Args a) {
         if (n0 + i < a.qcap) a.queue[n0 + i] = st[i];
 }
 
-// the root's packed key, passed by value (no host-to-device copy of host memory per search)
-struct RootKey {
-    uint64_t w[ACX_MAX_L / 16 + 2];
-};
-
 // root: node 0 (code 1), its key in the store and its table entry
 template <int KWM>
 __global__ void bfs_root_kernel(Args a, RootKey rk) {
@@ -535,15 +365,7 @@ __global__ void bfs_root_kernel(Args a, RootKey rk) {
     for (int k = 0; k < a.kw; ++k) a.store[k] = rk.w[k];
     const Key<KWM> key = kload<KWM>(a.store, a.kw);
     const uint64_t h = khash<KWM>(key, a.kw);
-    uint64_t* ent = a.table + (h & a.bmask) * BUCKET;
-    ent[0] = a.ep | (1ull << 24) | (uint32_t)(h >> 40);  // (a.ep is 0 in the key-in-table layout)
-    if (a.kt) {
-        uint64_t gd[3];
-        kt_guarded(key.w, a.kw, gd);
-        ent[1] = gd[0];
-        ent[2] = gd[1];
-        ent[3] = gd[2];
-    }
+    a.table[(h & a.bmask) * BUCKET] = visited::entry(a.ep, 1, visited::fp_of(h));
     a.queue[0] = 1;
 }
 
@@ -579,10 +401,9 @@ struct LiveMirror {
 };
 constexpr int RING = 4;
 
-// (6) close the chunk (one block, after commit), in the reference's order: a raising child
-// before the first success and not after the budget cut -> AssertionError; else a success not
-// after the cut -> the path; else the cut -> the budget message; else the next chunk; an empty
-// queue -> (False, None).  Then min_length: when the chunk's minimum child total beats the
+// (6) close the chunk (one block, after commit) with the reference's verdict (chunk_verdict):
+// AssertionError, the path, the budget message, or the next chunk; an empty queue -> (False,
+// None).  Then min_length: when the chunk's minimum child total beats the
 // running minimum, the parents whose minimum does are found with a prefix-min scan and walked
 // move by move, appending the reference's "New minimal length found" values
 // (breadth_first.py:79-82).  Then the state for the next chunk, the control block reset, and
@@ -596,21 +417,12 @@ __global__ __launch_bounds__(256) void bfs_close_kernel(Args a, int64_t k, LiveM
     const int t = threadIdx.x;
     Live* lv = a.live;
     const bool run = chunk_args(a);
-    bool ends = false, err_first = false, succ_first = false;
-    int64_t cut = INT64_MAX, err_p = INT64_MAX, suc_p = INT64_MAX;
+    Verdict v{};
     Ctl c;
     if (run && t == 0) {
         c = *a.ctl;
-        cut = c.cut_p == NONE ? INT64_MAX : (int64_t)c.cut_p;
-        err_p = c.err == NONE ? INT64_MAX : (int64_t)(c.err / 12);
-        suc_p = c.succ == NONE ? INT64_MAX : (int64_t)(c.succ / 12);
-        err_first = c.err != NONE && c.err < c.succ && err_p <= cut;
-        succ_first = !err_first && c.succ != NONE && suc_p <= cut;
-        ends = err_first || succ_first || cut != INT64_MAX;
-        // children the reference looks at in this chunk, in order: up to and including the
-        // success child, up to (not including) the raising child, through the cut parent
-        s_end = err_first ? c.err : succ_first ? c.succ + 1 : cut != INT64_MAX ? (uint32_t)((cut + 1) * 12)
-                                                                                : (uint32_t)a.P * 12u;
+        v = chunk_verdict(c.succ, c.err, c.cut_p, (uint32_t)a.P);
+        s_end = v.looked;
         s_trace = !c.overflow && c.min_len < lv->running;
         nlist = 0;
     }
@@ -668,17 +480,13 @@ __global__ __launch_bounds__(256) void bfs_close_kernel(Args a, int64_t k, LiveM
         if (c.overflow) {
             lv->status = -1;
             lv->stop = 1;
-        } else if (ends) {
-            const int64_t last = err_first ? err_p : succ_first ? suc_p : cut;
-            lv->parents += last + 1;
-            if (err_first) {
-                lv->status = ACX_BFS_MOVE_ERROR;
-            } else if (succ_first) {
-                lv->status = ACX_BFS_FOUND;
-                lv->succ_node = a.head + suc_p;
+        } else if (v.kind != 0) {
+            lv->parents += (int64_t)v.last_p + 1;
+            lv->status = v.kind;
+            if (v.kind == ACX_BFS_FOUND) {
+                lv->succ_node = a.head + v.last_p;
                 lv->succ_act = c.succ % 12;
-            } else {
-                lv->status = ACX_BFS_BUDGET;
+            } else if (v.kind == ACX_BFS_BUDGET) {
                 lv->n_nodes = (int64_t)c.nodes_at_cut;
             }
             lv->stop = 1;
@@ -742,7 +550,7 @@ struct Search {
                                    // and the destructor wait for it (any stream)
     bool fin_pending = false;
     int64_t kbase = 0;             // chunks enqueued by earlier searches
-    int epoch = 0;                 // 8-entry table: the last search's epoch (0: table all zero)
+    int epoch = 0;                 // the last search's epoch (0: table all zero)
     uint16_t* trace_host = nullptr;
     int32_t* path_dev = nullptr;    // pinned, coherent host memory: bfs_path_kernel writes the path
     int64_t* path_n_dev = nullptr;  // there directly (no device-to-host copy)
@@ -771,7 +579,6 @@ static constexpr int64_t PATH_CAP = 1 << 16;
 #define ACX_BFS_CHUNK_DEADLINE_S 30.0
 #endif
 static constexpr int ACX_E_TIMEOUT = -100;  // internal to acx_bfs_run (returned as ACX_E_LAUNCH)
-static int g_bfs_layout = 0;  // 0 default (8-entry table), 2 key-in-table where L allows (tests, A/B)
 
 template <class T>
 static bool dalloc(T*& p, size_t n) {
@@ -791,14 +598,7 @@ struct ChunkLaunch {
         const unsigned wb = (unsigned)((ntiles + TPB / WAVE - 1) / (TPB / WAVE));
         const int64_t nc = (int64_t)ntiles * TILE_CH;
         bfs_expand_kernel<NW><<<dim3((unsigned)ntiles), dim3(TPB), 0, st>>>(a);
-        bool kt_done = false;
-        if constexpr (NW <= 3) {  // L <= KT_MAX_L
-            if (a.kt) {
-                bfs_insert_kt_kernel<NW + 1><<<dim3((unsigned)((nc + TPB - 1) / TPB)), dim3(TPB), 0, st>>>(a);
-                kt_done = true;
-            }
-        }
-        if (!kt_done) bfs_insert_kernel<NW + 1><<<dim3((unsigned)((nc + TPB - 1) / TPB)), dim3(TPB), 0, st>>>(a);
+        bfs_insert_kernel<NW + 1><<<dim3((unsigned)((nc + TPB - 1) / TPB)), dim3(TPB), 0, st>>>(a);
         bfs_count_kernel<<<dim3(wb), dim3(TPB), 0, st>>>(a);
         bfs_scan_kernel<<<dim3(1), dim3(1024), 0, st>>>(a);
         bfs_commit_kernel<<<dim3(wb), dim3(TPB), 0, st>>>(a);
@@ -845,14 +645,9 @@ void* acx_bfs_create(int32_t L, int64_t max_nodes, int64_t chunk_parents, int32_
     // probe).  Other sizes, A/B on the final pipeline (profiles/r03/r03x_bfs_table_load.json):
     // half the entries 1.52 vs 1.47 ms at 10^7 and (load <= 1) 16.0 vs 13.7 ms at 10^8; twice
     // the entries within 1 % at 10^7 and 14.5 vs 13.4 ms at 10^8.
-    // Key-in-table (L <= KT_MAX_L, opt-in): 4 words per entry, entries >= 1.25x the same bound
-    // (2 per bucket; the bound counts a whole last chunk's children as new: the real load stays
-    // lower).  Measured slower than the 8-entry table (r03i: 2.11 vs 1.68 ms at 10^7 nodes, 20.0
-    // vs 14.2 ms at 10^8): the saved node-key reads cost less than the table's doubled footprint.
-    const bool kt = L <= KT_MAX_L && g_bfs_layout == 2;
     uint64_t ts = 1024;
     const uint64_t bound = (uint64_t)(S->qcap + 12 * S->pmax);
-    while (kt ? ts < 5 * bound : ts * ACX_BFS_TABLE_LOAD_PCT < 100 * bound) ts <<= 1;
+    while (ts < 2 * bound) ts <<= 1;
     S->tsize = ts;
     Args& a = S->a;
     bool ok = dalloc(a.store, (size_t)(S->scap * S->kw)) && dalloc(a.queue, (size_t)S->qcap) &&
@@ -873,17 +668,12 @@ void* acx_bfs_create(int32_t L, int64_t max_nodes, int64_t chunk_parents, int32_
         return nullptr;
     }
     a.bmask = ts / BUCKET - 1;
-    a.kt = kt ? 1 : 0;
     a.qcap = S->qcap;
     a.L = L;
     a.kw = S->kw;
     a.cyc = S->cyc;
     return S;
 }
-
-// test / A-B hook: 2 selects the key-in-table layout (L <= 43) for searches created afterwards,
-// 0 the default 8-entry table
-void acx_internal_bfs_layout(int32_t layout) { g_bfs_layout = layout; }
 
 void acx_bfs_destroy(void* h) { delete static_cast<Search*>(h); }
 
@@ -905,16 +695,7 @@ int acx_bfs_run(void* h, const int32_t* presentation, int64_t max_nodes, int32_t
         if (hipStreamWaitEvent(st, S->fin, 0) != hipSuccess) return ACX_E_LAUNCH;
         S->fin_pending = false;
     }
-    if (a.kt) {  // key-in-table entries have no epoch: cleared per search
-        if (hipMemsetAsync(a.table, 0, S->tsize * 8, st) != hipSuccess) return ACX_E_LAUNCH;
-        a.ep = 0;
-    } else {
-        if (++S->epoch == 64) {  // the epoch wraps: clear once every 63 searches
-            if (hipMemsetAsync(a.table, 0, S->tsize * 8, st) != hipSuccess) return ACX_E_LAUNCH;
-            S->epoch = 1;
-        }
-        a.ep = (uint64_t)S->epoch << EP_SHIFT;
-    }
+    if (!acx::visited::next_epoch(S->epoch, a.table, S->tsize * 8, st, a.ep)) return ACX_E_LAUNCH;
     by_nw(L, rl);
     bfs_init_kernel<<<dim3(1), dim3(64), 0, st>>>(a, max_nodes, S->pmax, (uint32_t)total0);
 

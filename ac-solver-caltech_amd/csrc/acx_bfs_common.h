@@ -1,6 +1,9 @@
-// acx_bfs_common.h -- pieces shared by the single-GPU device BFS (acx_bfs.hip) and the
-// owner-partitioned multi-GPU BFS (acx_sbfs.hip): packed-key compare / hash, table entry
-// tags, block scans.  The key format itself (field readers, pack_key) is acx_key.h.
+// acx_bfs_common.h -- pieces shared by the search engines on the device: the single-GPU BFS
+// (acx_bfs.hip), the batched BFS (acx_mbfs.hip), the owner-partitioned multi-GPU BFS
+// (acx_sbfs.hip) and the greedy search (acx_greedy.hip): packed-key compare / hash, the child
+// step, wave and block scans, the budget-cut predicate.  The key format itself (field readers,
+// pack_key) is acx_key.h, the visited-set format and insert acx_visited.h, the chunk verdict
+// acx_bfs_verdict.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -112,26 +115,82 @@ __device__ __forceinline__ uint64_t tload(const uint64_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// exclusive prefix sum of v over the block (TPB threads); total in `tot`
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sh, uint32_t& tot) {
-    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    uint32_t x = v;
+// inclusive prefix sum of x over the wave's lanes
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x, int lane) {
 #pragma unroll
     for (int o = 1; o < WAVE; o <<= 1) {
         const uint32_t y = __shfl_up(x, o, WAVE);
         if (lane >= o) x += y;
     }
+    return x;
+}
+
+// exclusive prefix sum of v over a block of N threads (sh: N / 64 words); total in `tot`
+template <int N>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sh, uint32_t& tot) {
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    const uint32_t x = wave_incl_sum(v, lane);
     if (lane == WAVE - 1) sh[wid] = x;
     __syncthreads();
     uint32_t off = 0;
     tot = 0;
 #pragma unroll
-    for (int i = 0; i < TPB / WAVE; ++i) {
+    for (int i = 0; i < N / WAVE; ++i) {
         off += i < wid ? sh[i] : 0u;
         tot += sh[i];
     }
     return off + x - v;
 }
+
+// exclusive scan of x[0..n) in place by one block of 1024 threads (sh: 16 words; thread t takes
+// a contiguous run of ceil(n / 1024) elements); returns the total.  each(i) is called once per
+// element, by the thread that owns it, in the summing pass: a caller that folds a second array
+// over the same indices shares that pass's memory round trips (a loop of its own after the scan
+// cost bfs_scan_kernel 3 us per chunk, 16.3 -> 19.5 us)
+template <class Each>
+__device__ __forceinline__ uint32_t scan_array_1024(uint32_t* x, int n, uint32_t* sh, Each each) {
+    const int per = (n + 1023) / 1024;
+    const int b0 = threadIdx.x * per, b1 = min(n, b0 + per);
+    uint32_t loc = 0;
+    for (int i = b0; i < b1; ++i) {
+        loc += x[i];
+        each(i);
+    }
+    uint32_t tot;
+    uint32_t run = block_excl_scan<1024>(loc, sh, tot);
+    for (int i = b0; i < b1; ++i) {
+        const uint32_t c = x[i];
+        x[i] = run;
+        run += c;
+    }
+    return tot;
+}
+__device__ __forceinline__ uint32_t scan_array_1024(uint32_t* x, int n, uint32_t* sh) {
+    return scan_array_1024(x, n, sh, [](int) {});
+}
+
+// The node-budget cut falls after the first parent through which len(tree_nodes) reaches
+// max_nodes: `base` / `incl` nodes appended by the chunk before / through the parent, need =
+// max_nodes - len(tree_nodes) before the chunk.  The reference tests after every parent, so a
+// budget that is already spent (need <= 0) cuts after the chunk's first parent.
+__host__ __device__ __forceinline__ bool budget_cut_after(int64_t base, int64_t incl, int64_t need, bool first_parent) {
+    return (base < need || first_parent) && incl >= need;
+}
+
+// the child of `parent` by move `act` (the parent's is_clean flag picks the move routine that
+// skips the reductions a clean word cannot need); returns the move's ACX_ERR_*
+template <int NW>
+__device__ __forceinline__ int child_of(const PresRegs<NW>& parent, bool clean, int act, int L, bool cyc,
+                                        PresRegs<NW>& child) {
+    child = parent;
+    return clean ? ac_move_clean<NW>(child.w0, child.n0, child.w1, child.n1, act, L, cyc)
+                 : ac_move<NW>(child.w0, child.n0, child.w1, child.n1, act, L, cyc);
+}
+
+// a root's packed key, passed to its kernel by value (no host-to-device copy per search)
+struct RootKey {
+    uint64_t w[ACX_MAX_L / 16 + 2];
+};
 
 __device__ __forceinline__ uint32_t block_min(uint32_t v, uint32_t* sh) {
     const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;

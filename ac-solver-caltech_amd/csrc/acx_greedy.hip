@@ -34,6 +34,7 @@
 
 #include "acx_bfs_common.h"
 #include "acx_frontier.h"
+#include "acx_visited.h"
 
 namespace acx {
 namespace greedy {
@@ -43,9 +44,9 @@ using bfs::Key;
 using bfs::keq;
 using bfs::khash;
 using bfs::kload;
+using visited::BUCKET;  // the table shares acx_visited.h's bucket and fingerprint format; entries
+using visited::FP_MASK;  // are (id + 1) << 24 | fp with no epoch, probed and committed below
 
-constexpr int BUCKET = 8;
-constexpr uint32_t FP_MASK = 0xffffffu;
 constexpr int64_t AGE = 1 << 16;  // a cached expansion stays usable while fewer nodes than this have been
                                   // appended since its probe (bounds the in-flight table: two
                                   // generations of AGE nodes, 2 x 1 MB of tagged entries, cache-
@@ -86,11 +87,10 @@ template <int NW>
 __device__ __forceinline__ void expand_lane(const DevArgs& a, int t) {
     if (t >= a.n * ACT) return;
     const int p = t / ACT, act = t - p * ACT;
-    PresRegs<NW> q;
-    load_key<NW>(a.parents + (int64_t)p * a.kw, a.kw, a.L, q);
+    PresRegs<NW> pr, q;
+    load_key<NW>(a.parents + (int64_t)p * a.kw, a.kw, a.L, pr);
     const bool cyc = a.cyc != 0;
-    const int e = is_clean<NW>(q.w0, q.n0, q.w1, q.n1, cyc) ? ac_move_clean<NW>(q.w0, q.n0, q.w1, q.n1, act, a.L, cyc)
-                                                             : ac_move<NW>(q.w0, q.n0, q.w1, q.n1, act, a.L, cyc);
+    const int e = bfs::child_of<NW>(pr, is_clean<NW>(pr.w0, pr.n0, pr.w1, pr.n1, cyc), act, a.L, cyc, q);
     if (e != ACX_ERR_NONE) {
         q.n0 = 0xff;
         q.n1 = 0xff;

@@ -11,8 +11,7 @@
 //   store  (B, kw) uint64   node keys in discovery order = FIFO order (node 0 is the root), so the
 //                           queue is the store itself and `head` is the next parent's index;
 //   meta   (B) uint32       parent index << 4 | action of each node (the path reader walks it);
-//   table  (nb * 8) uint64  the visited set: buckets of 8 entries (one 64-B line per probe),
-//                           entry = epoch << 58 | code << 24 | 24-bit fingerprint, nb buckets with
+//   table  (nb * 8) uint64  the visited set (acx_visited.h: buckets of 8 entries), nb buckets with
 //                           8 nb >= 2 (B + 11 + 768) -- load <= 1/2 -- chosen by range reduction
 //                           of the hash (no power-of-two rounding);
 //   scratch (768, kw) uint64  only for L > 64: the round's child keys (below).
@@ -20,19 +19,19 @@
 //   8 kw B + 4 B + 64 ceil((B + 779) / 4) + 32 [+ 6144 kw when L > 64],   kw = acx_key_words(L).
 //
 // A round takes the next P <= 64 parents (nodes head .. head + P) and runs, with a barrier between:
-//   expand  lane = parent, wave w makes actions 3w..3w+2 (the mapping of bfs_expand_kernel); the
+//   expand  lane = parent, wave w makes actions 3w..3w+2 (child_of, acx_bfs_common.h); the
 //           768 child keys go to LDS in sequential order s = 12 p + a (L <= 64: at most 30 KiB;
 //           above that 54 KiB of LDS would halve the workgroups per CU, so they go to the
 //           search's scratch in HBM); first success and first raising child by LDS atomicMin;
-//   insert  thread per child s below the first success / raising child: probe the table; a code
+//   insert  thread per child s below the first success / raising child: visited::insert; a code
 //           below n (the nodes before the round) names a stored node, a code n + s a child of this
-//           round, so the full key is compared in the store or in the round's keys.  First
-//           occurrence wins by atomicMin on the entry, the replaced child is told (`lost`), as in
-//           bfs_insert_kernel.  A probe that has walked all nb buckets sets the overflow status;
+//           round, so the full key is compared in the store or in the round's keys.  The first
+//           occurrence holds the entry, the child it replaced is told (`lost`).  A probe that has
+//           walked all nb buckets sets the overflow status;
 //   decide  wave 0: survivors per parent, their prefix sum, the first parent after which
-//           len(tree_nodes) >= max_nodes, and the reference's verdict for the round exactly as
-//           bfs_close_kernel takes it (raising child / success / budget cut, the earliest in
-//           sequential order; otherwise the next round, or queue exhaustion);
+//           len(tree_nodes) >= max_nodes, and the reference's verdict for the round
+//           (chunk_verdict, acx_bfs_verdict.h: raising child / success / budget cut, the earliest
+//           in sequential order; otherwise the next round, or queue exhaustion);
 //   commit  (no verdict yet) the survivors' keys are appended in (parent, action) order with
 //           their meta word, and each survivor's table entry is rewritten from its round code to
 //           its node index; the running minimum takes the child totals up to the ending event.
@@ -44,7 +43,7 @@
 // another node a round later, so no stale value may be read (node codes in acx_bfs.hip are
 // permanent, which is why its plain bucket loads are safe there).  Nothing needs a wider scope:
 // a search's memory is touched by its own workgroup alone.  A handle is reusable: entries
-// carry the run's 6-bit epoch and the tables are cleared when it wraps, as in acx_bfs.hip.
+// carry the run's epoch (visited::next_epoch).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -54,18 +53,17 @@
 #include "acx_moves.h"
 
 #include "acx_bfs_common.h"
+#include "acx_bfs_verdict.h"
+#include "acx_visited.h"
 
 namespace acx {
 namespace mbfs {
 
 using namespace acx::bfs;
+using visited::BUCKET;
 
 constexpr int RP = 64;          // parents per round
 constexpr int RC = 12 * RP;     // children per round
-constexpr int BUCKET = 8;       // table entries per bucket (64 B)
-constexpr uint32_t FP_MASK = 0xffffffu;
-constexpr int EP_SHIFT = 58;
-constexpr uint64_t CODE_MASK = (1ull << 34) - 1;
 constexpr int64_t MAX_NODES_EACH = 1ll << 24;
 constexpr int RKW = ACX_MAX_L / 16 + 2;  // words of the largest key, rounded up
 
@@ -91,7 +89,7 @@ struct Args {
     int64_t* path_len;
     int64_t cap;  // B: node rows per search
     uint32_t nb;  // buckets per search
-    uint64_t ep;  // this run's epoch << EP_SHIFT
+    uint64_t ep;  // this run's epoch, shifted (visited::next_epoch)
     int L, kw, cyc;
 };
 
@@ -100,6 +98,30 @@ struct Args {
 // the L2 on every round for nobody's benefit)
 __device__ __forceinline__ uint64_t wload(const uint64_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// one search's visited set: nb buckets, the first by range reduction of the hash; a bucket line
+// is read entry by entry with wload (a round code means another node a round later, so no stale
+// value may be read)
+struct Buckets {
+    using Index = uint32_t;
+    uint64_t* table;
+    uint32_t nb;
+    __device__ __forceinline__ Index buckets() const { return nb; }
+    __device__ __forceinline__ Index first(uint64_t h) const { return __umulhi((uint32_t)h, nb); }
+    __device__ __forceinline__ Index next(Index b) const { return b + 1 == nb ? 0 : b + 1; }
+    __device__ __forceinline__ uint64_t* bucket(Index b) const { return table + (uint64_t)b * BUCKET; }
+    __device__ __forceinline__ void load(const uint64_t* bk, uint64_t (&e)[BUCKET]) const {
+#pragma unroll
+        for (int j = 0; j < BUCKET; ++j) e[j] = wload(bk + j);
+    }
+};
+
+// edges from the root to node `v` of a search (meta: parent index << 4 | action), at most cap
+__device__ __forceinline__ int64_t path_depth(const uint32_t* meta, int64_t v, int64_t cap) {
+    int64_t d = 0;
+    for (int64_t i = v; i != 0 && d < cap; i = meta[i] >> 4) ++d;
+    return d;
 }
 
 static inline uint32_t buckets_for(int64_t cap) { return (uint32_t)((2 * (cap + 11 + RC) + BUCKET - 1) / BUCKET); }
@@ -176,8 +198,9 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
     if (tid == 0) {
         const Key<NW + 1> key = kload<NW + 1>(rk, kw);
         const uint64_t h = khash<NW + 1>(key, kw);
-        __hip_atomic_store(table + (uint64_t)__umulhi((uint32_t)h, a.nb) * BUCKET, a.ep | (uint32_t)(h >> 40),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // node 0
+        const Buckets tb{table, a.nb};
+        __hip_atomic_store(tb.bucket(tb.first(h)), visited::entry(a.ep, 0, visited::fp_of(h)), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);  // node 0
         meta[0] = 0;
     }
     __syncthreads();
@@ -208,9 +231,8 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
                 for (int j = 0; j < 3; ++j) {
                     const int act = wid * 3 + j;
                     const uint32_t s = (uint32_t)lane * 12u + (uint32_t)act;
-                    PresRegs<NW> c = pr;
-                    const int e = clean ? ac_move_clean<NW>(c.w0, c.n0, c.w1, c.n1, act, L, cyc)
-                                        : ac_move<NW>(c.w0, c.n0, c.w1, c.n1, act, L, cyc);
+                    PresRegs<NW> c;
+                    const int e = child_of<NW>(pr, clean, act, L, cyc, c);
                     if (e != ACX_ERR_NONE) {
                         err = min(err, s);
                     } else {
@@ -241,55 +263,18 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
             if ((uint32_t)c >= end0) continue;
             const uint64_t code = NB + (uint64_t)c;
             const Key<NW + 1> key = kload<NW + 1>(ck + c * kw, kw);
-            const uint64_t h = khash<NW + 1>(key, kw);
-            const uint32_t fp = (uint32_t)(h >> 40);
-            const uint64_t my = a.ep | (code << 24) | fp;
-            uint32_t b = __umulhi((uint32_t)h, a.nb);
-            int done = 0;  // 1 seen / lost, 2 holds the entry
-            for (uint32_t it = 0; !done; ++it) {
-                if (it >= a.nb) {
-                    s_over = 1;
-                    break;
-                }
-                uint64_t* bk = table + (uint64_t)b * BUCKET;
-                uint64_t e[BUCKET];
-#pragma unroll
-                for (int j = 0; j < BUCKET; ++j) e[j] = wload(bk + j);
-#pragma unroll
-                for (int j = 0; j < BUCKET && !done; ++j) {
-                    uint64_t v = e[j];
-                    if ((v >> EP_SHIFT) != (a.ep >> EP_SHIFT)) {  // empty in this run
-                        const uint64_t old = atomicCAS((unsigned long long*)(bk + j), (unsigned long long)v,
-                                                       (unsigned long long)my);
-                        if (old == v) {
-                            done = 2;
-                            slot[c] = b * BUCKET + j;
-                            break;
-                        }
-                        v = old;  // claimed meanwhile: a value of this search
-                    }
-                    if (((uint32_t)v & FP_MASK) != fp) continue;
-                    const uint64_t vc = (v >> 24) & CODE_MASK;
-                    const bool eq = vc < NB ? keq<NW + 1>(store + vc * kw, key, kw)
-                                            : keq<NW + 1>(ck + (vc - NB) * kw, key, kw);
-                    if (!eq) continue;
-                    if (vc < code) {  // a node, or an earlier child of the round
-                        done = 1;
-                        break;
-                    }
-                    const uint64_t old = atomicMin((unsigned long long*)(bk + j), (unsigned long long)my);
-                    if (old < my) {
-                        done = 1;
-                    } else {  // replaced a later child of the round: it learns it lost
-                        const uint64_t lc = ((old >> 24) & CODE_MASK) - NB;
-                        if (lc < (uint64_t)RC) lost[lc] = 1;
-                        done = 2;
-                        slot[c] = b * BUCKET + j;
-                    }
-                }
-                b = b + 1 == a.nb ? 0 : b + 1;
-            }
-            cand[c] = done == 2;
+            const visited::Outcome ins = visited::insert(
+                Buckets{table, a.nb}, a.ep, code, khash<NW + 1>(key, kw),
+                [&](uint64_t vc) {
+                    return vc < NB ? keq<NW + 1>(store + vc * kw, key, kw) : keq<NW + 1>(ck + (vc - NB) * kw, key, kw);
+                },
+                [&](uint32_t sl, uint64_t displaced) {  // a later child of the round that held it learns it lost
+                    slot[c] = sl;
+                    const uint64_t lc = displaced - NB;
+                    if (displaced != visited::NO_CODE && lc < (uint64_t)RC) lost[lc] = 1;
+                });
+            if (ins == visited::FULL) s_over = 1;
+            cand[c] = ins == visited::HELD;
         }
         __syncthreads();
         if (s_over) break;  // (uniform) cannot happen at load <= 1/2
@@ -305,12 +290,7 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
                 }
             }
             const uint32_t cnt = __popc(m);
-            uint32_t x = cnt;
-#pragma unroll
-            for (int o = 1; o < WAVE; o <<= 1) {
-                const uint32_t y = __shfl_up(x, o, WAVE);
-                if (lane >= o) x += y;
-            }
+            const uint32_t x = wave_incl_sum(cnt, lane);
             pmask[lane] = m;
             pexcl[lane] = x - cnt;
             const uint32_t total = __shfl(x, WAVE - 1, WAVE);
@@ -318,16 +298,12 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
             const unsigned long long cutb = __ballot(lane < P && n_nodes + (int64_t)x >= max_nodes);
             const uint32_t cutp = cutb ? (uint32_t)__builtin_ctzll(cutb) : NONE;
             const uint32_t at_cut = __shfl(x, cutb ? (int)cutp : 0, WAVE);
-            const uint32_t succ = s_succ, err = s_err;
-            const bool err_first = err != NONE && err < succ && err / 12 <= cutp;
-            const bool succ_first = !err_first && succ != NONE && succ / 12 <= cutp;
+            const Verdict v = chunk_verdict(s_succ, s_err, cutp, (uint32_t)P);
             if (lane == 0) {
-                s_dec[0] = err_first ? ACX_BFS_MOVE_ERROR : succ_first ? ACX_BFS_FOUND : cutb ? ACX_BFS_BUDGET : 0;
-                // children the reference looks at in this round: up to (not including) the raising
-                // child, up to and including the success child, through the cut parent, or all
-                s_dec[1] = err_first ? err : succ_first ? succ + 1 : cutb ? (cutp + 1) * 12u : (uint32_t)nch;
-                s_dec[2] = err_first ? err / 12 : succ_first ? succ / 12 : cutp;
-                s_dec[3] = (err_first || succ_first || !cutb) ? total : at_cut;
+                s_dec[0] = (uint32_t)v.kind;
+                s_dec[1] = v.looked;
+                s_dec[2] = v.last_p;
+                s_dec[3] = v.kind == ACX_BFS_BUDGET ? at_cut : total;
                 s_min = NONE;
             }
         }
@@ -346,7 +322,7 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
                 meta[pos] = ((uint32_t)(head + p) << 4) | (uint32_t)act;
                 uint64_t* ent = table + slot[c];
                 const uint64_t v = wload(ent);
-                __hip_atomic_store(ent, (v & ~(CODE_MASK << 24)) | ((uint64_t)pos << 24), __ATOMIC_RELAXED,
+                __hip_atomic_store(ent, visited::entry_recode(v, (uint64_t)pos), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
@@ -379,12 +355,8 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
     }
 
     if (tid == 0) {
-        int64_t plen = 0;
-        if (status == ACX_BFS_FOUND) {
-            int64_t d = 0;
-            for (int64_t i = succ_node; i != 0 && d < a.cap; i = meta[i] >> 4) ++d;
-            plen = d + 2;  // [(-1, total0)] + the edges to the parent + (action, 2)
-        }
+        // [(-1, total0)] + the edges to the parent + (action, 2)
+        const int64_t plen = status == ACX_BFS_FOUND ? path_depth(meta, succ_node, a.cap) + 2 : 0;
         a.status[q] = status;
         a.nodes[q] = status < 0 ? 0 : n_nodes;
         a.parents[q] = parents;
@@ -403,8 +375,7 @@ __global__ __launch_bounds__(TPB) void mbfs_path_kernel(Args a, int64_t n, const
     if (r.status != ACX_BFS_FOUND) return;
     const uint64_t* store = a.store + q * a.cap * a.kw;
     const uint32_t* meta = a.meta + q * a.cap;
-    int64_t d = 0;
-    for (int64_t i = r.succ_node; i != 0 && d < a.cap; i = meta[i] >> 4) ++d;
+    const int64_t d = path_depth(meta, r.succ_node, a.cap);
     const int64_t off = offsets[q];
     if (off < 0 || off + d + 2 > out_cap) return;
     actions[off] = -1;
@@ -495,12 +466,8 @@ int acx_mbfs_run(void* h, const int32_t* states, const int64_t* budgets, int64_t
     if (n < 0 || n > S->n_cap) return ACX_E_ARG;
     if (n == 0) return ACX_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (++S->epoch == 64) {  // the epoch wraps: clear once every 63 runs
-        if (hipMemsetAsync(S->a.table, 0, S->table_bytes, st) != hipSuccess) return ACX_E_LAUNCH;
-        S->epoch = 1;
-    }
     Args& a = S->a;
-    a.ep = (uint64_t)S->epoch << EP_SHIFT;
+    if (!acx::visited::next_epoch(S->epoch, a.table, S->table_bytes, st, a.ep)) return ACX_E_LAUNCH;
     a.states = states;
     a.budgets = budgets;
     a.status = status;

@@ -140,7 +140,7 @@ __device__ __forceinline__ uint32_t owner_of(uint64_t h, int world) {
 
 // (1) block per tile of 64 candidate local parents lo + j (j < Pr = min(P, nloc - lo); the
 // parents of the chunk are the prefix with gid < head + P); wave w makes the children of actions
-// 3w..3w+2 of the same 64 parents (as acx_bfs.hip's bfs_expand_kernel: 4x the lanes of a
+// 3w..3w+2 of the same 64 parents (child_of; as in the single-GPU expansion, 4x the lanes of a
 // lane-per-parent loop over 12 serial moves), owners counted by ballots.  The block's 64 x 12
 // child keys and owners are staged in LDS and written parent-major (the chunk's sequence order)
 // as one contiguous run, so the insert and the commit read them in order; for NW > 4 (L > 64,
@@ -184,9 +184,8 @@ __global__ __launch_bounds__(TPB, NW <= 4 ? 6 : 4) void sbfs_expand_kernel(Args 
         const int act = wid * SAPW + jj;
         uint32_t own = 0xff;
         if (live) {
-            PresRegs<NW> q = pr;
-            const int e = clean ? ac_move_clean<NW>(q.w0, q.n0, q.w1, q.n1, act, a.L, cyc)
-                                : ac_move<NW>(q.w0, q.n0, q.w1, q.n1, act, a.L, cyc);
+            PresRegs<NW> q;
+            const int e = child_of<NW>(pr, clean, act, a.L, cyc, q);
             const uint32_t s = p * 12u + (uint32_t)act;
             if (e != ACX_ERR_NONE) {
                 err = min(err, s);
@@ -254,27 +253,6 @@ __global__ __launch_bounds__(TPB, NW <= 4 ? 6 : 4) void sbfs_expand_kernel(Args 
     for (int i = threadIdx.x; i < a.world; i += TPB) x[2 + i] = hist[i];
 }
 
-// exclusive scan over a 1024-thread block (sh: 16 words)
-__device__ __forceinline__ uint32_t block_excl_scan_1024(uint32_t v, uint32_t* sh, uint32_t& tot) {
-    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, WAVE);
-        if (lane >= o) x += y;
-    }
-    if (lane == WAVE - 1) sh[wid] = x;
-    __syncthreads();
-    uint32_t off = 0;
-    tot = 0;
-#pragma unroll
-    for (int i = 0; i < 1024 / WAVE; ++i) {
-        off += i < wid ? sh[i] : 0u;
-        tot += sh[i];
-    }
-    return off + x - v;
-}
-
 // (1b) the expand blocks' records -> the chunk's min child total, local parent count and
 // children per owner (one block); each block's per-owner count is replaced by its exclusive
 // prefix over the blocks, and ctl->cur[o] set to owner o's first send slot, so pack places
@@ -313,7 +291,7 @@ __global__ __launch_bounds__(1024) void sbfs_expand_reduce_kernel(Args a, int nb
         for (int b = b0; b < b1; ++b) loc += a.xblk[(size_t)b * rw + 2 + o];
         __syncthreads();  // red reuse
         uint32_t total;
-        uint32_t run = block_excl_scan_1024(loc, &red[0][0], total);
+        uint32_t run = block_excl_scan<1024>(loc, &red[0][0], total);
         for (int b = b0; b < b1; ++b) {
             uint32_t* x = a.xblk + (size_t)b * rw + 2 + o;
             const uint32_t c = *x;
@@ -373,9 +351,9 @@ __global__ __launch_bounds__(TPB) void sbfs_pack_kernel(Args a) {
 }
 
 // (3a) probe / claim / join, one lane per child this rank owns: its own children in place
-// (records r < 12 Pr, ckeys) and the received ones; as acx_bfs.hip's bfs_insert_kernel, the first
-// occurrence of a state within the chunk keeps the entry (atomicMin), a child it displaces is
-// marked lost
+// (records r < 12 Pr, ckeys) and the received ones; as with acx_visited.h's insert, the first
+// occurrence of a state within the chunk keeps the entry, a child it displaces is marked lost
+// (the table format differs: see "Table entries" above)
 template <int KWM>
 __global__ __launch_bounds__(TPB, 8) void sbfs_insert_kernel(Args a) {  // 8 waves/SIMD (latency-bound)
     const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -487,9 +465,9 @@ __global__ __launch_bounds__(TPB) void sbfs_count_kernel(Args a) {
         }
     }
     uint32_t tot, ltot;
-    block_excl_scan(__popc(m), sh, tot);
+    block_excl_scan<TPB>(__popc(m), sh, tot);
     __syncthreads();
-    block_excl_scan(__popc(mine), sh, ltot);
+    block_excl_scan<TPB>(__popc(mine), sh, ltot);
     if (threadIdx.x == 0) {
         a.bsum[blockIdx.x] = tot;
         a.lbsum[blockIdx.x] = ltot;
@@ -498,38 +476,15 @@ __global__ __launch_bounds__(TPB) void sbfs_count_kernel(Args a) {
 
 // (4b) exclusive scans of x[0..nb) and y[0..nb) in place, one block of 1024 (both arrays in one
 // launch); the totals into *tx, *ty
-__device__ __forceinline__ void scan_1024(uint32_t* x, int nb, uint64_t* total, uint32_t* sh) {
-    const int t = threadIdx.x, lane = t & (WAVE - 1), wid = t / WAVE;
-    const int per = (nb + 1023) / 1024;
-    const int b0 = t * per, b1 = min(nb, b0 + per);
-    uint32_t loc = 0;
-    for (int i = b0; i < b1; ++i) loc += x[i];
-    uint32_t v = loc;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t y = __shfl_up(v, o, WAVE);
-        if (lane >= o) v += y;
-    }
-    if (lane == WAVE - 1) sh[wid] = v;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-    for (int i = 0; i < 1024 / WAVE; ++i) {
-        off += i < wid ? sh[i] : 0u;
-        tot += sh[i];
-    }
-    uint32_t run = off + v - loc;
-    for (int i = b0; i < b1; ++i) {
-        const uint32_t c = x[i];
-        x[i] = run;
-        run += c;
-    }
-    if (t == 0) *total = tot;
-    __syncthreads();  // sh reuse
-}
 __global__ __launch_bounds__(1024) void sbfs_scan_kernel(uint32_t* x, uint32_t* y, int nb, uint64_t* tx, uint64_t* ty) {
     __shared__ uint32_t sh[1024 / WAVE];
-    scan_1024(x, nb, tx, sh);
-    scan_1024(y, nb, ty, sh);
+    const uint32_t sx = scan_array_1024(x, nb, sh);
+    __syncthreads();  // sh reuse
+    const uint32_t sy = scan_array_1024(y, nb, sh);
+    if (threadIdx.x == 0) {
+        *tx = sx;
+        *ty = sy;
+    }
 }
 
 // (4c) global ids, the budget cut, and the appends to this rank's store.  A block's own
@@ -547,14 +502,14 @@ __global__ __launch_bounds__(TPB) void sbfs_commit_kernel(Args a) {
     const uint32_t m = p < a.P ? a.gmask[p] : 0u;
     const uint32_t mine = p < a.P ? a.mine[p] : 0u;
     uint32_t tot;
-    const uint32_t bex = block_excl_scan(__popc(m), sh, tot);  // survivors of the block before p
+    const uint32_t bex = block_excl_scan<TPB>(__popc(m), sh, tot);  // survivors of the block before p
     const int64_t base = (int64_t)a.bsum[blockIdx.x] + bex;
     __syncthreads();
     uint32_t ltot;
-    const uint32_t lrank = block_excl_scan(__popc(mine), sh, ltot);
+    const uint32_t lrank = block_excl_scan<TPB>(__popc(mine), sh, ltot);
     if (p < a.P) {
         const int64_t incl = base + __popc(m);
-        if (incl >= a.need && (base < a.need || p == 0)) {
+        if (budget_cut_after(base, incl, a.need, p == 0)) {
             a.ctl->cut_p = (uint32_t)p;
             a.ctl->nodes_at_cut = (uint64_t)(a.n_before + incl);
         }
@@ -601,7 +556,7 @@ __global__ __launch_bounds__(TPB) void sbfs_commit_kernel(Args a) {
         a.arena[(a.abase + r) * a.kw + c] = a.recv[(int64_t)(r - n_own) * (a.kw + 1) + c];
     }
     uint32_t bs;
-    block_excl_scan(stored, sh, bs);  // (its barrier: every read of the block's sslot / srec is done)
+    block_excl_scan<TPB>(stored, sh, bs);  // (its barrier: every read of the block's sslot / srec is done)
     if (threadIdx.x == 0 && bs) atomicAdd(&a.ctl->stored, bs);
     // the block's seqs back to SEEN / not lost for the next chunk (no per-chunk memset);
     // consecutive threads on consecutive seqs
@@ -706,10 +661,6 @@ __global__ void sbfs_lookup_kernel(Args a, int64_t g) {
         a.look[3] = pr.n0 + pr.n1;
     }
 }
-
-struct RootKey {
-    uint64_t w[ACX_MAX_L / 16 + 2];
-};
 
 template <int KWM>
 __global__ void sbfs_root_kernel(Args a, RootKey rk) {

@@ -403,21 +403,12 @@ def search_starts(L, cyc):
     return picked
 
 
-def _layout_hook():
-    import ctypes
-    from acx import _lib
-    hook = _lib.load().acx_internal_bfs_layout
-    hook.argtypes = [ctypes.c_int32]
-    hook.restype = None
-    return hook
-
-
 @pytest.mark.parametrize("L", [36, 65, 128])
 @pytest.mark.parametrize("cyc", [False, True])
 def test_planted_bfs_engines_store_the_oracle_bfs(L, cyc, capsys):
-    """The device BFS at chunk 0 and 3, its key-in-table layout (L <= 43), the sharded BFS at one rank
-    and the host engine from planted starts, budget 200 (the root, its 12 children, theirs): the same
-    node keys in the same order as a plain FIFO + dedup BFS over O.expand12."""
+    """The device BFS at chunk 0 and 3, the sharded BFS at one rank and the host engine from planted
+    starts, budget 200 (the root, its 12 children, theirs): the same node keys in the same order as
+    a plain FIFO + dedup BFS over O.expand12."""
     from acx.search import _device_bfs as D
     from acx.search import _engine as E
     from acx.search import _sharded_bfs as S
@@ -433,16 +424,6 @@ def test_planted_bfs_engines_store_the_oracle_bfs(L, cyc, capsys):
             assert D.device_bfs(start, BUDGET, cyclically_reduce_after_moves=cyc, device=DEV, chunk=chunk,
                                 keep_node_keys=True) == (False, None)
             check(f"device bfs chunk {chunk}", D.LAST_STATS["nodes"], D.LAST_STATS["node_keys"])
-        if L <= 43:
-            hook = _layout_hook()
-            D.release_workspaces()
-            hook(2)
-            try:
-                D.device_bfs(start, BUDGET, cyclically_reduce_after_moves=cyc, device=DEV, keep_node_keys=True)
-            finally:
-                hook(0)
-                D.release_workspaces()
-            check("device bfs key-in-table", D.LAST_STATS["nodes"], D.LAST_STATS["node_keys"])
         assert S.sharded_bfs(start, BUDGET, cyclically_reduce_after_moves=cyc, device=DEV, chunk=3,
                              keep_node_keys=True) == (False, None)
         assert np.array_equal(S.LAST_STATS["node_ids"][:n], np.arange(n))
