@@ -94,6 +94,12 @@ SIGNATURES = {
     "acx_mbfs_run": ([_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "acx_mbfs_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
     "acx_mbfs_destroy": ([_P], None),
+    # batched greedy, one wave per search (ac-solver-caltech_amd/csrc/acx_mgreedy.hip)
+    "acx_mgreedy_bytes": ([_I32, _I64], ctypes.c_int64),
+    "acx_mgreedy_create": ([_I32, _I64, _I64, _I32], ctypes.c_void_p),
+    "acx_mgreedy_run": ([_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    "acx_mgreedy_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
+    "acx_mgreedy_destroy": ([_P], None),
     # owner-partitioned multi-GPU BFS (ac-solver-caltech_amd/csrc/acx_sbfs.hip)
     "acx_sbfs_create": ([_I32, _I64, _I64, _I32, _I32, _I32], ctypes.c_void_p),
     "acx_sbfs_destroy": ([_P], None),

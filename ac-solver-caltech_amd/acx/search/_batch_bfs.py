@@ -12,40 +12,63 @@ from .. import _lib
 
 _HANDLES = {}  # (device, L, cyclical) -> (handle, searches, max_nodes_each)
 MAX_NODES_EACH = 1 << 24
+
 # default workspace_bytes: this fraction of the device memory free at the call.  Half leaves the
 # caller's own tensors and the allocator's cached blocks alone; a batch that needs more is split
 # into consecutive groups, one launch each.
 WORKSPACE_FRACTION = 0.5
 
 
-def _handle(lib, dev: torch.device, L: int, cyclical: bool, n: int, max_nodes: int):
+class _Engine:
+    """One batched search of the library: the C functions `prefix`_bytes / _create / _run / _paths /
+    _destroy, its cached handles, and which searches return a path.  _batch_greedy.py runs the
+    batched greedy search through the same code."""
+
+    def __init__(self, name, prefix, handles, path_statuses, no_path):
+        self.name, self.prefix, self.handles = name, prefix, handles
+        self.path_statuses, self.no_path = path_statuses, no_path
+
+    def fn(self, lib, what):
+        return getattr(lib, f"{self.prefix}_{what}")
+
+
+_BFS = _Engine("bfs_many", "acx_mbfs", _HANDLES, (_lib.BFS_FOUND,), (False, None))
+
+
+def _handle(eng, lib, dev: torch.device, L: int, cyclical: bool, n: int, max_nodes: int):
     key = (dev.index, L, bool(cyclical))
-    h = _HANDLES.get(key)
+    h = eng.handles.get(key)
     if h is not None and h[1] >= n and h[2] >= max_nodes:
         return h[0]
     if h is not None:
-        lib.acx_mbfs_destroy(h[0])
-        del _HANDLES[key]
+        eng.fn(lib, "destroy")(h[0])
+        del eng.handles[key]
     with torch.cuda.device(dev):
-        ptr = lib.acx_mbfs_create(L, n, max_nodes, int(bool(cyclical)))
+        ptr = eng.fn(lib, "create")(L, n, max_nodes, int(bool(cyclical)))
     if not ptr:
-        raise _lib.ACXError(f"acx_mbfs_create(L={L}, n_searches={n}, max_nodes_each={max_nodes}) failed "
+        raise _lib.ACXError(f"{eng.prefix}_create(L={L}, n_searches={n}, max_nodes_each={max_nodes}) failed "
                             "(device memory?)")
-    _HANDLES[key] = (ptr, n, max_nodes)
+    eng.handles[key] = (ptr, n, max_nodes)
     return ptr
 
 
-def release_workspaces() -> None:
-    """Free the cached batch workspaces."""
-    if not _HANDLES:
+def _release(eng) -> None:
+    if not eng.handles:
         return
     lib = _lib.load()
-    for ptr, _, _ in _HANDLES.values():
-        lib.acx_mbfs_destroy(ptr)
-    _HANDLES.clear()
+    for ptr, _, _ in eng.handles.values():
+        eng.fn(lib, "destroy")(ptr)
+    eng.handles.clear()
 
 
-def _validate(presentations, max_nodes_to_explore, on_error):
+def release_workspaces() -> None:
+    """Free the cached batch workspaces (the batched greedy search's too)."""
+    _release(_BFS)
+    from . import _batch_greedy
+    _batch_greedy.release_workspaces()
+
+
+def _validate(presentations, max_nodes_to_explore, on_error, name="bfs_many"):
     """(states (N, 2L) int32, budgets (N) int64) or ValueError; no GPU call (a tensor on a GPU is
     copied to the host to be checked)."""
     if on_error not in ("raise", "return"):
@@ -84,7 +107,7 @@ def _validate(presentations, max_nodes_to_explore, on_error):
         b = b.astype(np.int64)
     b = np.maximum(b, 1)  # the reference still expands the root once
     if N and int(b.max()) > MAX_NODES_EACH:
-        raise ValueError("bfs_many supports at most 2^24 nodes per search")
+        raise ValueError(f"{name} supports at most 2^24 nodes per search")
     return np.ascontiguousarray(p, dtype=np.int32), b
 
 
@@ -102,41 +125,47 @@ def bfs_many(presentations, max_nodes_to_explore=10000, cyclically_reduce_after_
       expanded, min_length.
     workspace_bytes: the most device memory the searches' workspace may take (default: half of the
       free device memory); a larger batch runs as consecutive groups, one launch per group."""
-    states, budgets = _validate(presentations, max_nodes_to_explore, on_error)
+    return _search_many(_BFS, presentations, max_nodes_to_explore, cyclically_reduce_after_moves, device, on_error,
+                        return_stats, workspace_bytes)
+
+
+def _search_many(eng, presentations, max_nodes_to_explore, cyclically_reduce_after_moves, device, on_error,
+                 return_stats, workspace_bytes):
+    states, budgets = _validate(presentations, max_nodes_to_explore, on_error, eng.name)
     N, L = states.shape[0], states.shape[1] // 2
     stats = dict(status=np.zeros(N, np.int32), nodes=np.zeros(N, np.int64), parents=np.zeros(N, np.int64),
                  min_length=np.zeros(N, np.int32))
-    results = [(False, None)] * N
+    results = [eng.no_path] * N
     if N:
         dev = torch.device(device if device is not None else "cuda")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
         lib = _lib.load()
         cap = int(budgets.max())
-        per = int(lib.acx_mbfs_bytes(L, cap))
+        per = int(eng.fn(lib, "bytes")(L, cap))
         if workspace_bytes is None:
             workspace_bytes = int(WORKSPACE_FRACTION * torch.cuda.mem_get_info(dev)[0])
-            have = _HANDLES.get((dev.index, L, bool(cyclically_reduce_after_moves)))
+            have = eng.handles.get((dev.index, L, bool(cyclically_reduce_after_moves)))
             if have is not None:  # a cached workspace is not free memory, but it is ours to use
-                workspace_bytes = max(workspace_bytes, have[1] * int(lib.acx_mbfs_bytes(L, have[2])))
+                workspace_bytes = max(workspace_bytes, have[1] * int(eng.fn(lib, "bytes")(L, have[2])))
         group = max(1, min(N, int(workspace_bytes) // per))
         for g0 in range(0, N, group):
             g1 = min(N, g0 + group)
-            _run_group(lib, dev, L, bool(cyclically_reduce_after_moves), states[g0:g1], budgets[g0:g1], group, cap,
-                       g0, stats, results)
+            _run_group(eng, lib, dev, L, bool(cyclically_reduce_after_moves), states[g0:g1], budgets[g0:g1], group,
+                       cap, g0, stats, results)
     errs = np.nonzero(stats["status"] == _lib.BFS_MOVE_ERROR)[0]
     if len(errs):
         if on_error == "raise":
-            raise AssertionError("bfs_many: a move produced an invalid presentation (utils.py:264-266) in searches "
+            raise AssertionError(f"{eng.name}: a move produced an invalid presentation (utils.py:264-266) in searches "
                                  f"{errs.tolist()}")
         for i in errs:
             results[int(i)] = None
     return (results, stats) if return_stats else results
 
 
-def _run_group(lib, dev, L, cyclical, states, budgets, n_cap, cap, g0, stats, results):
+def _run_group(eng, lib, dev, L, cyclical, states, budgets, n_cap, cap, g0, stats, results):
     n = len(states)
-    h = _handle(lib, dev, L, cyclical, n_cap, cap)
+    h = _handle(eng, lib, dev, L, cyclical, n_cap, cap)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
         st = torch.from_numpy(states).to(dev)
@@ -144,8 +173,9 @@ def _run_group(lib, dev, L, cyclical, states, budgets, n_cap, cap, g0, stats, re
         status = torch.empty(n, dtype=torch.int32, device=dev)
         min_len = torch.empty(n, dtype=torch.int32, device=dev)
         nodes, parents, plen = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
-        _lib.check(lib.acx_mbfs_run(h, st.data_ptr(), bd.data_ptr(), n, status.data_ptr(), nodes.data_ptr(),
-                                    parents.data_ptr(), min_len.data_ptr(), plen.data_ptr(), stream), "acx_mbfs_run")
+        _lib.check(eng.fn(lib, "run")(h, st.data_ptr(), bd.data_ptr(), n, status.data_ptr(), nodes.data_ptr(),
+                                      parents.data_ptr(), min_len.data_ptr(), plen.data_ptr(), stream),
+                   f"{eng.prefix}_run")
         ends = torch.cumsum(plen, 0)
         offsets = ends - plen
         plen_h = plen.cpu().numpy()  # (waits for the searches)
@@ -153,8 +183,8 @@ def _run_group(lib, dev, L, cyclical, states, budgets, n_cap, cap, g0, stats, re
         acts = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
         tots = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
         if total:
-            _lib.check(lib.acx_mbfs_paths(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), total, stream),
-                       "acx_mbfs_paths")
+            _lib.check(eng.fn(lib, "paths")(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), total, stream),
+                       f"{eng.prefix}_paths")
         status_h = status.cpu().numpy()
         stats["status"][g0:g0 + n] = status_h
         stats["nodes"][g0:g0 + n] = nodes.cpu().numpy()
@@ -163,11 +193,12 @@ def _run_group(lib, dev, L, cyclical, states, budgets, n_cap, cap, g0, stats, re
         acts_h, tots_h = acts.cpu().tolist(), tots.cpu().tolist()
     bad = np.nonzero(status_h < 0)[0]
     if len(bad):  # validated rows and budgets cannot get here: a full table or a kernel fault
-        raise _lib.ACXError(f"acx_mbfs_run: searches {(bad + g0).tolist()} ended with status "
+        raise _lib.ACXError(f"{eng.prefix}_run: searches {(bad + g0).tolist()} ended with status "
                             f"{status_h[bad].tolist()}")
     off = 0
     for i in range(n):
         k = int(plen_h[i])
-        if status_h[i] == _lib.BFS_FOUND:
-            results[g0 + i] = (True, list(zip(acts_h[off:off + k], tots_h[off:off + k])))
+        if status_h[i] in eng.path_statuses:
+            results[g0 + i] = (bool(status_h[i] == _lib.BFS_FOUND),
+                               list(zip(acts_h[off:off + k], tots_h[off:off + k])))
         off += k

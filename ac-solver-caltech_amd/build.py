@@ -19,8 +19,8 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "acx", "libacx.so")
 INCLUDE = os.path.join(REPO, "include")
-SOURCES = ["acx_kernels.hip", "acx_bfs.hip", "acx_mbfs.hip", "acx_sbfs.hip", "acx_features.hip", "acx_curriculum.hip",
-           "acx_words.hip", "acx_greedy.hip", "acx_search.cpp"]
+SOURCES = ["acx_kernels.hip", "acx_bfs.hip", "acx_mbfs.hip", "acx_mgreedy.hip", "acx_sbfs.hip", "acx_features.hip",
+           "acx_curriculum.hip", "acx_words.hip", "acx_greedy.hip", "acx_search.cpp"]
 # acx_kernels.hip is also compiled once per instantiation part (-DACX_PART=n, see the part table
 # and its "extern template" block in acx_launch.h), in parallel: the runtime-L generic sets took
 # ~7 minutes in one object

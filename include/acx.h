@@ -439,6 +439,44 @@ int acx_mbfs_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions,
 void acx_mbfs_destroy(void* h);
 
 /*
+ * Greedy search over a batch of presentations in one launch (csrc/acx_mgreedy.hip): one workgroup
+ * (one wave) owns one search from root to verdict -- node store, visited set and the frontier, a
+ * min-heap ordered as Python orders (total, path length, tuple(state)) (csrc/acx_prio.h) -- on a
+ * private slice of the handle's workspace.  Every search gives the result of greedy_search on its
+ * own presentation, ac_solver/search/greedy.py:15-121.
+ *   acx_mgreedy_bytes   (greedy.py:15-121) workspace bytes per search for budgets up to
+ *                       max_nodes_each = B at max_relator_length L, kw = acx_key_words(L):
+ *                         (8 kw + 20) (B + 11) + 64 ceil((B + 23) / 4) + 32
+ *                       (B + 11 rows -- the budget is tested once per pop, after up to 12 appends
+ *                       -- of node key, parent/action word, depth and a 12-byte heap entry; a
+ *                       visited set at load <= 1/2 of B + 11 + 12 entries; the verdict record);
+ *                       ACX_E_ARG for L outside [1, ACX_MAX_L] or B outside [1, 2^24].
+ *   acx_mgreedy_create  (greedy.py:15-121) allocates n_searches times that on the current
+ *                       device; NULL on bad arguments or when the workspace does not fit.
+ *   acx_mgreedy_run     (greedy.py:71-119) searches n <= n_searches presentations: `states`
+ *                       DEVICE (n, 2L) int32, `budgets` DEVICE (n) int64 (a budget < 1 behaves as
+ *                       1), outputs DEVICE arrays of n: status (an ACX_BFS_* value,
+ *                       ACX_MBFS_DOMAIN or ACX_MBFS_OVERFLOW as in acx_mbfs_run), nodes
+ *                       (len(tree_nodes) at the ending event), parents (nodes popped), min_length,
+ *                       path_len (entries of the returned path: greedy returns one unless a move
+ *                       raised, so it is 0 only on ACX_BFS_MOVE_ERROR or a negative status).
+ *                       Asynchronous on `stream`.  A handle is reusable.
+ *   acx_mgreedy_paths   (greedy.py:100,121) after a run, on the same stream: for every search with
+ *                       a path, [(-1, total0), (action, total), ...] in CSR form as
+ *                       acx_mbfs_paths writes it -- on ACX_BFS_FOUND the path to the trivial
+ *                       child, otherwise the last popped node's path plus (11, total of its last
+ *                       child).
+ *   acx_mgreedy_destroy (greedy.py:15-121) frees the workspace.
+ */
+int64_t acx_mgreedy_bytes(int32_t L, int64_t max_nodes_each);
+void* acx_mgreedy_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t cyclical);
+int acx_mgreedy_run(void* h, const int32_t* states, const int64_t* budgets, int64_t n, int32_t* status, int64_t* nodes,
+                    int64_t* parents, int32_t* min_length, int64_t* path_len, void* stream);
+int acx_mgreedy_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
+                      void* stream);
+void acx_mgreedy_destroy(void* h);
+
+/*
  * Breadth-first search with the node store and the visited set partitioned over G GPUs by key
  * owner (one process per GPU).  Same results as acx_bfs_run / the
  * reference bfs (breadth_first.py:15-97).  The caller runs the same chunk loop on every rank
