@@ -88,18 +88,6 @@ SIGNATURES = {
     "acx_bfs_destroy": ([_P], None),
     "acx_bfs_node_keys": ([_P, _P, _I64, _P], ctypes.c_int64),
     "acx_bfs_min_trace": ([_P, _P, _I64], ctypes.c_int64),
-    # batched BFS, one workgroup per search (ac-solver-caltech_amd/csrc/acx_mbfs.hip)
-    "acx_mbfs_bytes": ([_I32, _I64], ctypes.c_int64),
-    "acx_mbfs_create": ([_I32, _I64, _I64, _I32], ctypes.c_void_p),
-    "acx_mbfs_run": ([_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P], ctypes.c_int),
-    "acx_mbfs_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
-    "acx_mbfs_destroy": ([_P], None),
-    # batched greedy, one wave per search (ac-solver-caltech_amd/csrc/acx_mgreedy.hip)
-    "acx_mgreedy_bytes": ([_I32, _I64], ctypes.c_int64),
-    "acx_mgreedy_create": ([_I32, _I64, _I64, _I32], ctypes.c_void_p),
-    "acx_mgreedy_run": ([_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P], ctypes.c_int),
-    "acx_mgreedy_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
-    "acx_mgreedy_destroy": ([_P], None),
     # owner-partitioned multi-GPU BFS (ac-solver-caltech_amd/csrc/acx_sbfs.hip)
     "acx_sbfs_create": ([_I32, _I64, _I64, _I32, _I32, _I32], ctypes.c_void_p),
     "acx_sbfs_destroy": ([_P], None),
@@ -115,6 +103,17 @@ SIGNATURES = {
     "acx_sbfs_trace": ([_P, _I64, _I64, _P, _I64, _P], ctypes.c_int64),
     "acx_sbfs_node_keys": ([_P, _P, _P, _I64, _P], ctypes.c_int64),
 }
+
+# the batched engines, one workgroup per search: BFS (ac-solver-caltech_amd/csrc/acx_mbfs.hip) and
+# greedy (acx_mgreedy.hip) have the same five functions (the handle of csrc/acx_batch.h)
+_BATCH = (("bytes", [_I32, _I64], ctypes.c_int64),
+          ("create", [_I32, _I64, _I64, _I32], ctypes.c_void_p),
+          ("run", [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+          ("paths", [_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
+          ("destroy", [_P], None))
+for _prefix in ("acx_mbfs", "acx_mgreedy"):
+    for _what, _args, _res in _BATCH:
+        SIGNATURES[f"{_prefix}_{_what}"] = (_args, _res)
 
 _lib = None
 

@@ -39,19 +39,19 @@
 // store needs B rows.  Every loop is bounded: rounds by max_nodes (each expands >= 1 of fewer than
 // max_nodes nodes), probes by nb, the path walks by the node count.
 //
-// Table reads are workgroup-scope atomic loads and the rewrite an atomic store: a round code means
-// another node a round later, so no stale value may be read (node codes in acx_bfs.hip are
-// permanent, which is why its plain bucket loads are safe there).  Nothing needs a wider scope:
-// a search's memory is touched by its own workgroup alone.  A handle is reusable: entries
-// carry the run's epoch (visited::next_epoch).
+// The frame around the round -- the root and its refusal statuses, the table view with its
+// workgroup-scope reads (node codes in acx_bfs.hip are permanent, which is why its plain bucket
+// loads are safe there; a round code here means another node a round later), the result record,
+// the path reader and the reusable handle behind acx_mbfs_* -- is acx_batch.h, shared with
+// acx_mgreedy.hip.  The insert call stays here: as a shared routine it cost mgreedy_kernel<8>
+// 14 VGPRs (95 -> 109) in every shape tried.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <new>
 
 #include "acx.h"
 #include "acx_moves.h"
 
+#include "acx_batch.h"
 #include "acx_bfs_common.h"
 #include "acx_bfs_verdict.h"
 #include "acx_visited.h"
@@ -60,154 +60,49 @@ namespace acx {
 namespace mbfs {
 
 using namespace acx::bfs;
+using batch::Buckets;
+using batch::Res;
 using visited::BUCKET;
 
 constexpr int RP = 64;          // parents per round
 constexpr int RC = 12 * RP;     // children per round
-constexpr int64_t MAX_NODES_EACH = 1ll << 24;
-constexpr int RKW = ACX_MAX_L / 16 + 2;  // words of the largest key, rounded up
 
-// what the path reader needs of a finished search
-struct Res {
-    int32_t status, succ_act;
-    int64_t succ_node;  // the parent of the success child
-    int64_t nodes, pad;
-};
-
-struct Args {
-    const int32_t* states;   // (n, 2L)
-    const int64_t* budgets;  // (n)
-    uint64_t* store;
-    uint32_t* meta;
-    uint64_t* table;
+struct Args : batch::Args {
     uint64_t* scratch;
-    Res* res;
-    int32_t* status;
-    int64_t* nodes;
-    int64_t* parents;
-    int32_t* min_length;
-    int64_t* path_len;
-    int64_t cap;  // B: node rows per search
-    uint32_t nb;  // buckets per search
-    uint64_t ep;  // this run's epoch, shifted (visited::next_epoch)
-    int L, kw, cyc;
 };
-
-// a table entry as the workgroup last wrote it: only this workgroup touches its search's table, so
-// workgroup scope is the whole of it (an agent-scope load or fence would go through, or write back,
-// the L2 on every round for nobody's benefit)
-__device__ __forceinline__ uint64_t wload(const uint64_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// one search's visited set: nb buckets, the first by range reduction of the hash; a bucket line
-// is read entry by entry with wload (a round code means another node a round later, so no stale
-// value may be read)
-struct Buckets {
-    using Index = uint32_t;
-    uint64_t* table;
-    uint32_t nb;
-    __device__ __forceinline__ Index buckets() const { return nb; }
-    __device__ __forceinline__ Index first(uint64_t h) const { return __umulhi((uint32_t)h, nb); }
-    __device__ __forceinline__ Index next(Index b) const { return b + 1 == nb ? 0 : b + 1; }
-    __device__ __forceinline__ uint64_t* bucket(Index b) const { return table + (uint64_t)b * BUCKET; }
-    __device__ __forceinline__ void load(const uint64_t* bk, uint64_t (&e)[BUCKET]) const {
-#pragma unroll
-        for (int j = 0; j < BUCKET; ++j) e[j] = wload(bk + j);
-    }
-};
-
-// edges from the root to node `v` of a search (meta: parent index << 4 | action), at most cap
-__device__ __forceinline__ int64_t path_depth(const uint32_t* meta, int64_t v, int64_t cap) {
-    int64_t d = 0;
-    for (int64_t i = v; i != 0 && d < cap; i = meta[i] >> 4) ++d;
-    return d;
-}
-
-static inline uint32_t buckets_for(int64_t cap) { return (uint32_t)((2 * (cap + 11 + RC) + BUCKET - 1) / BUCKET); }
 
 template <int NW>
 __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
     constexpr bool LDS_KEYS = NW <= 4;
     __shared__ uint64_t kl[LDS_KEYS ? RC * (NW + 1) : 1];
-    __shared__ uint64_t rk[RKW];
     __shared__ uint32_t slot[RC];    // table index of the entry a child holds
     __shared__ uint16_t ctot[RC];    // child total, 0xffff: the move raised (or no such child)
     __shared__ uint8_t cand[RC];     // the child holds its state's entry after its own probe
     __shared__ uint8_t lost[RC];     // an earlier child of the round took that entry
     __shared__ uint32_t pmask[RP], pexcl[RP];
-    __shared__ uint32_t s_succ, s_err, s_min, s_over, s_bad;
-    __shared__ uint32_t s_n[2];
+    __shared__ uint32_t s_succ, s_err, s_min, s_over;
     __shared__ uint32_t s_dec[4];    // verdict kind, children looked at, last parent, new nodes
 
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
     const int64_t q = blockIdx.x;
     const int L = a.L, kw = a.kw;
     const bool cyc = a.cyc != 0;
-    uint64_t* store = a.store + q * a.cap * kw;
-    uint32_t* meta = a.meta + q * a.cap;
+    uint64_t* store = a.store + q * a.rows * kw;
+    uint32_t* meta = a.meta + q * a.rows;
     uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
     uint64_t* ck;
     if constexpr (LDS_KEYS) ck = kl;
     else ck = a.scratch + q * (int64_t)RC * kw;
 
-    // the root: packed by the block (acx_key.h format), checked against the packed domain
-    if (tid < RKW) rk[tid] = 0;
-    if (tid < 2) s_n[tid] = 0;
-    if (tid == 0) s_bad = s_over = 0;
-    __syncthreads();
-    if (tid < 2 * L) {
-        const int32_t* st = a.states + q * 2 * L;
-        const int32_t v = st[tid];
-        const int h = tid >= L, i = tid - h * L;
-        bool bad = v < -2 || v > 2;
-        if (v == 0) {
-            bad = i + 1 < L && st[tid + 1] != 0;  // zeros only as right padding
-        } else if (!bad) {
-            const int bit = 2 * tid;
-            atomicOr((unsigned long long*)&rk[bit >> 6], (unsigned long long)(key_code(v) << (bit & 63)));
-            atomicAdd(&s_n[h], 1u);
-        }
-        if (bad) s_bad = 1;
-    }
-    __syncthreads();
-    int64_t max_nodes = a.budgets[q];
-    if (max_nodes < 1) max_nodes = 1;  // the reference still expands the root once
-    const uint32_t total0 = s_n[0] + s_n[1];
-    const bool dom = s_bad || s_n[0] == 0 || s_n[1] == 0;
-    if (dom || max_nodes > a.cap) {
-        if (tid == 0) {
-            const int32_t st = dom ? ACX_MBFS_DOMAIN : ACX_MBFS_OVERFLOW;
-            a.status[q] = st;
-            a.nodes[q] = 0;
-            a.parents[q] = 0;
-            a.min_length[q] = 0;
-            a.path_len[q] = 0;
-            a.res[q] = Res{st, 0, 0, 0, 0};
-        }
-        return;
-    }
-    if (tid == 0) {
-        const uint64_t lens = (uint64_t)s_n[0] | ((uint64_t)s_n[1] << 8);
-        const int bit = 4 * L;
-        rk[bit / 64] |= lens << (bit % 64);
-        if (bit % 64 > 48 && bit / 64 + 1 < kw) rk[bit / 64 + 1] |= lens >> (64 - bit % 64);
-    }
-    __syncthreads();
-    if (tid < kw) store[tid] = rk[tid];
-    if (tid == 0) {
-        const Key<NW + 1> key = kload<NW + 1>(rk, kw);
-        const uint64_t h = khash<NW + 1>(key, kw);
-        const Buckets tb{table, a.nb};
-        __hip_atomic_store(tb.bucket(tb.first(h)), visited::entry(a.ep, 0, visited::fp_of(h)), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_WORKGROUP);  // node 0
-        meta[0] = 0;
-    }
+    if (tid == 0) s_over = 0;
+    const batch::Root root = batch::root_setup<TPB, NW>(a, q, store, meta, table);
+    if (root.refused) return;
+    const int64_t max_nodes = root.max_nodes;
     __syncthreads();
 
     int64_t head = 0, n_nodes = 1, parents = 0, succ_node = 0;
     int32_t status = ACX_MBFS_OVERFLOW, succ_act = 0;
-    uint32_t running = total0;
+    uint32_t running = root.total0;
 
     for (int64_t round = 0; round <= max_nodes; ++round) {
         const int P = (int)(n_nodes - head < RP ? n_nodes - head : RP);
@@ -317,13 +212,10 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
                 const uint32_t m = pmask[p];
                 if (!((m >> act) & 1u)) continue;
                 const int64_t pos = n_nodes + pexcl[p] + __popc(m & ((1u << act) - 1u));
-                if (pos >= a.cap) continue;  // (never: a round without a verdict ends below max_nodes)
+                if (pos >= a.rows) continue;  // (never: a round without a verdict ends below max_nodes)
                 for (int k = 0; k < kw; ++k) store[pos * kw + k] = ck[c * kw + k];
                 meta[pos] = ((uint32_t)(head + p) << 4) | (uint32_t)act;
-                uint64_t* ent = table + slot[c];
-                const uint64_t v = wload(ent);
-                __hip_atomic_store(ent, visited::entry_recode(v, (uint64_t)pos), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+                batch::recode_entry(table, slot[c], (uint64_t)pos);
             }
         }
         {
@@ -355,139 +247,57 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
     }
 
     if (tid == 0) {
-        // [(-1, total0)] + the edges to the parent + (action, 2)
-        const int64_t plen = status == ACX_BFS_FOUND ? path_depth(meta, succ_node, a.cap) + 2 : 0;
-        a.status[q] = status;
-        a.nodes[q] = status < 0 ? 0 : n_nodes;
-        a.parents[q] = parents;
-        a.min_length[q] = (int32_t)running;
-        a.path_len[q] = plen;
-        a.res[q] = Res{status, succ_act, succ_node, n_nodes, 0};
+        // [(-1, total0)] + the edges to the success child's parent + (action, 2)
+        const int64_t plen = status == ACX_BFS_FOUND ? batch::path_depth(meta, succ_node, a.rows) + 2 : 0;
+        batch::write_result(a, q, Res{status, succ_act, succ_node, 2, 0, n_nodes}, parents, running, plen);
     }
 }
 
-// the reference's path of every found search: thread per search, written at offsets[q]
-__global__ __launch_bounds__(TPB) void mbfs_path_kernel(Args a, int64_t n, const int64_t* offsets, int32_t* actions,
-                                                        int32_t* totals, int64_t out_cap) {
-    const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (q >= n) return;
-    const Res r = a.res[q];
-    if (r.status != ACX_BFS_FOUND) return;
-    const uint64_t* store = a.store + q * a.cap * a.kw;
-    const uint32_t* meta = a.meta + q * a.cap;
-    const int64_t d = path_depth(meta, r.succ_node, a.cap);
-    const int64_t off = offsets[q];
-    if (off < 0 || off + d + 2 > out_cap) return;
-    actions[off] = -1;
-    totals[off] = key_total(store, a.L);
-    int64_t pos = off + d;
-    for (int64_t i = r.succ_node; i != 0 && pos > off; i = meta[i] >> 4, --pos) {
-        actions[pos] = (int32_t)(meta[i] & 15u);
-        totals[pos] = key_total(store + i * a.kw, a.L);
+// what the handle (acx_batch.h) needs of this engine
+struct Engine {
+    using Args = mbfs::Args;
+    static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND;
+    static int64_t rows_for(int64_t B) { return B; }
+    static uint32_t buckets_for(int64_t B) { return (uint32_t)((2 * (B + 11 + RC) + BUCKET - 1) / BUCKET); }
+    template <class F>
+    static void arrays(Args& a, F f) {
+        const size_t R = (size_t)a.rows, kw = (size_t)a.kw;
+        f(a.store, 8 * kw * R, false);
+        f(a.meta, 4 * R, false);
+        f(a.table, 8 * (size_t)BUCKET * a.nb, true);
+        f(a.res, sizeof(Res), true);
+        f(a.scratch, a.L > 64 ? 8 * kw * RC : 0, false);  // the round's child keys where they do not stay in LDS
     }
-    actions[off + d + 1] = r.succ_act;
-    totals[off + d + 1] = 2;
-}
-
-struct Batch {
-    int64_t n_cap = 0;
-    int epoch = 0;  // the last run's epoch (0: tables all zero)
-    size_t table_bytes = 0;
-    Args a{};
-
-    ~Batch() {
-        void* ptrs[] = {a.store, a.meta, a.table, a.scratch, a.res};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-    }
-};
-
-struct RunLaunch {
-    Batch* S;
-    hipStream_t st;
-    int64_t n;
     template <int NW>
-    void go() { mbfs_kernel<NW><<<dim3((unsigned)n), dim3(TPB), 0, st>>>(S->a); }
+    static void launch(const Args& a, int64_t n, hipStream_t st) {
+        mbfs_kernel<NW><<<dim3((unsigned)n), dim3(TPB), 0, st>>>(a);
+    }
 };
-
-static size_t scratch_bytes(int L, int kw) { return L > 64 ? (size_t)RC * kw * 8 : 0; }
 
 }  // namespace mbfs
 }  // namespace acx
 
-using namespace acx::mbfs;
+using acx::mbfs::Engine;
+namespace batch = acx::batch;
 
 extern "C" {
 
-int64_t acx_mbfs_bytes(int32_t L, int64_t max_nodes_each) {
-    if (L < 1 || L > ACX_MAX_L || max_nodes_each < 1 || max_nodes_each > MAX_NODES_EACH) return ACX_E_ARG;
-    const int kw = acx_key_words(L);
-    return (int64_t)(8 * (size_t)kw * max_nodes_each + 4 * (size_t)max_nodes_each +
-                     (size_t)buckets_for(max_nodes_each) * BUCKET * 8 + sizeof(Res) + scratch_bytes(L, kw));
-}
+int64_t acx_mbfs_bytes(int32_t L, int64_t max_nodes_each) { return batch::bytes<Engine>(L, max_nodes_each); }
 
 void* acx_mbfs_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t cyclical) {
-    if (L < 1 || L > ACX_MAX_L || n_searches < 1 || n_searches > (1ll << 24) || max_nodes_each < 1 ||
-        max_nodes_each > MAX_NODES_EACH)
-        return nullptr;
-    Batch* S = new (std::nothrow) Batch();
-    if (!S) return nullptr;
-    Args& a = S->a;
-    a.L = L;
-    a.kw = acx_key_words(L);
-    a.cyc = cyclical != 0;
-    a.cap = max_nodes_each;
-    a.nb = buckets_for(max_nodes_each);
-    S->n_cap = n_searches;
-    const size_t n = (size_t)n_searches;
-    S->table_bytes = n * a.nb * BUCKET * 8;
-    const size_t sb = scratch_bytes(L, a.kw);
-    bool ok = hipMalloc((void**)&a.store, n * (size_t)a.cap * a.kw * 8) == hipSuccess &&
-              hipMalloc((void**)&a.meta, n * (size_t)a.cap * 4) == hipSuccess &&
-              hipMalloc((void**)&a.table, S->table_bytes) == hipSuccess &&
-              hipMalloc((void**)&a.res, n * sizeof(Res)) == hipSuccess &&
-              (sb == 0 || hipMalloc((void**)&a.scratch, n * sb) == hipSuccess) &&
-              hipMemset(a.table, 0, S->table_bytes) == hipSuccess &&
-              hipMemset(a.res, 0, n * sizeof(Res)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete S;
-        return nullptr;
-    }
-    return S;
+    return batch::create<Engine>(L, n_searches, max_nodes_each, cyclical);
 }
 
-void acx_mbfs_destroy(void* h) { delete static_cast<Batch*>(h); }
+void acx_mbfs_destroy(void* h) { batch::destroy<Engine>(h); }
 
 int acx_mbfs_run(void* h, const int32_t* states, const int64_t* budgets, int64_t n, int32_t* status, int64_t* nodes,
                  int64_t* parents, int32_t* min_length, int64_t* path_len, void* stream) {
-    Batch* S = static_cast<Batch*>(h);
-    if (!S || !states || !budgets || !status || !nodes || !parents || !min_length || !path_len) return ACX_E_ARG;
-    if (n < 0 || n > S->n_cap) return ACX_E_ARG;
-    if (n == 0) return ACX_OK;
-    hipStream_t st = (hipStream_t)stream;
-    Args& a = S->a;
-    if (!acx::visited::next_epoch(S->epoch, a.table, S->table_bytes, st, a.ep)) return ACX_E_LAUNCH;
-    a.states = states;
-    a.budgets = budgets;
-    a.status = status;
-    a.nodes = nodes;
-    a.parents = parents;
-    a.min_length = min_length;
-    a.path_len = path_len;
-    RunLaunch rl{S, st, n};
-    by_nw(a.L, rl);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return batch::run<Engine>(h, states, budgets, n, status, nodes, parents, min_length, path_len, stream);
 }
 
 int acx_mbfs_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
                    void* stream) {
-    Batch* S = static_cast<Batch*>(h);
-    if (!S || !offsets || !actions || !totals || n < 0 || n > S->n_cap || cap < 0) return ACX_E_ARG;
-    if (n == 0) return ACX_OK;
-    mbfs_path_kernel<<<dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream>>>(S->a, n, offsets,
-                                                                                                 actions, totals, cap);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return batch::paths<Engine>(h, n, offsets, actions, totals, cap, stream);
 }
 
 }  // extern "C"

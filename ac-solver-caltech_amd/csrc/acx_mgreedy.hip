@@ -48,20 +48,19 @@
 // Every loop is bounded: pops by the rows (each pop removes one of at most R appended nodes),
 // sifts by the heap height, probes by nb, the path walk by the node's depth.
 //
-// The heap, the store and the table are shared by the lanes across phases.  Table reads are
-// workgroup-scope atomic loads and the rewrite an atomic store, as in acx_mbfs.hip (a pop's code
-// means another child a pop later, so no stale value may be read); everything else is plain
-// loads and stores ordered by the barriers.  Nothing needs a wider scope: a search's memory is
-// touched by its own workgroup alone.  A handle is reusable: table entries carry the run's epoch
-// (visited::next_epoch), and every other array is written before it is read.
+// The heap, the store and the table are shared by the lanes across phases: table reads are
+// workgroup-scope atomic loads and the rewrite an atomic store (a pop's code means another child a
+// pop later, so no stale value may be read); everything else is plain loads and stores ordered by
+// the barriers.  The frame around the pop -- the root and its refusal statuses, the table view,
+// the result record, the path reader and the reusable handle behind acx_mgreedy_* -- is
+// acx_batch.h, shared with acx_mbfs.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <new>
 
 #include "acx.h"
 #include "acx_moves.h"
 
+#include "acx_batch.h"
 #include "acx_bfs_common.h"
 #include "acx_prio.h"
 #include "acx_visited.h"
@@ -70,68 +69,23 @@ namespace acx {
 namespace mgreedy {
 
 using namespace acx::bfs;
+using batch::Buckets;
+using batch::Res;
 using visited::BUCKET;
 
 constexpr int GT = WAVE;        // threads per search: one wave (the ballots below rely on it)
 constexpr int FAN = 64;         // heap fan-out = lanes of the wave
 constexpr int LEVELS = 5;       // 1 + 64 + 64^2 + 64^3 + 64^4 > 2^24 + 11 entries
 constexpr int OVERSHOOT = 11;   // nodes a pop can append past the budget
-constexpr int64_t MAX_NODES_EACH = 1ll << 24;
-constexpr int RKW = ACX_MAX_L / 16 + 2;  // words of the largest key, rounded up
 static_assert(GT == WAVE && FAN == WAVE, "one wave per search");
 
-// what the path reader needs of a finished search: the path is the one to `end_node` (the success
-// child's parent, or the last popped node) plus (last_act, last_tot)
-struct Res {
-    int32_t status, last_act;
-    int64_t end_node;
-    int32_t last_tot, pad;
-    int64_t nodes;
-};
-
-struct Args {
-    const int32_t* states;   // (n, 2L)
-    const int64_t* budgets;  // (n)
-    uint64_t* store;
-    uint32_t* meta;
-    uint32_t* depth;
+struct Args : batch::Args {  // (depth is batch::Args's)
     uint64_t* hk;
     uint32_t* hid;
-    uint64_t* table;
-    Res* res;
-    int32_t* status;
-    int64_t* nodes;
-    int64_t* parents;
-    int32_t* min_length;
-    int64_t* path_len;
-    int64_t maxb;  // B: the largest budget a search may have
-    int64_t rows;  // R = B + 11
-    uint32_t nb;   // buckets per search
-    uint64_t ep;   // this run's epoch, shifted (visited::next_epoch)
-    int L, kw, cyc;
 };
 
-// a table entry as the workgroup last wrote it (acx_mbfs.hip: workgroup scope is the whole of it)
-__device__ __forceinline__ uint64_t wload(const uint64_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-struct Buckets {
-    using Index = uint32_t;
-    uint64_t* table;
-    uint32_t nb;
-    __device__ __forceinline__ Index buckets() const { return nb; }
-    __device__ __forceinline__ Index first(uint64_t h) const { return __umulhi((uint32_t)h, nb); }
-    __device__ __forceinline__ Index next(Index b) const { return b + 1 == nb ? 0 : b + 1; }
-    __device__ __forceinline__ uint64_t* bucket(Index b) const { return table + (uint64_t)b * BUCKET; }
-    __device__ __forceinline__ void load(const uint64_t* bk, uint64_t (&e)[BUCKET]) const {
-#pragma unroll
-        for (int j = 0; j < BUCKET; ++j) e[j] = wload(bk + j);
-    }
-};
-
-static inline int64_t rows_for(int64_t B) { return B + OVERSHOOT; }
-static inline uint32_t buckets_for(int64_t B) { return (uint32_t)((2 * (rows_for(B) + 12) + BUCKET - 1) / BUCKET); }
+// greedy returns a path unless a move raised
+constexpr uint32_t WITH_PATH = 1u << ACX_BFS_EXHAUSTED | 1u << ACX_BFS_FOUND | 1u << ACX_BFS_BUDGET;
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int o) {
     const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, WAVE);
@@ -174,11 +128,9 @@ template <int NW>
 __global__ __launch_bounds__(GT) void mgreedy_kernel(Args a) {
     __shared__ uint64_t ck[12 * (NW + 1)];  // the pop's child keys, kw words each
     __shared__ uint64_t tk[WAVE * (NW + 1)];  // full keys of heap entries whose hk tie (take)
-    __shared__ uint64_t rk[RKW];
     __shared__ uint32_t slot[12];   // table index of the entry a child holds
     __shared__ uint32_t ctot[12];   // child total
     __shared__ uint32_t lost[12];   // an earlier child of the pop took that entry
-    __shared__ uint32_t s_n[2], s_bad;
 
     const int lane = threadIdx.x;
     const int64_t q = blockIdx.x;
@@ -191,61 +143,12 @@ __global__ __launch_bounds__(GT) void mgreedy_kernel(Args a) {
     uint32_t* hid = a.hid + q * a.rows;
     uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
 
-    // the root: packed by the wave (acx_key.h format), checked against the packed domain
-    if (lane < RKW) rk[lane] = 0;
-    if (lane < 2) s_n[lane] = 0;
-    if (lane == 0) s_bad = 0;
-    __syncthreads();
-    {
-        const int32_t* st = a.states + q * 2 * L;
-        for (int t = lane; t < 2 * L; t += GT) {
-            const int32_t v = st[t];
-            const int h = t >= L, i = t - h * L;
-            bool bad = v < -2 || v > 2;
-            if (v == 0) {
-                bad = i + 1 < L && st[t + 1] != 0;  // zeros only as right padding
-            } else if (!bad) {
-                const int bit = 2 * t;
-                atomicOr((unsigned long long*)&rk[bit >> 6], (unsigned long long)(key_code(v) << (bit & 63)));
-                atomicAdd(&s_n[h], 1u);
-            }
-            if (bad) s_bad = 1;
-        }
-    }
-    __syncthreads();
-    int64_t max_nodes = a.budgets[q];
-    if (max_nodes < 1) max_nodes = 1;  // the reference still expands the root once
-    const uint32_t total0 = s_n[0] + s_n[1];
-    const bool dom = s_bad || s_n[0] == 0 || s_n[1] == 0;
-    if (dom || max_nodes > a.maxb) {
-        if (lane == 0) {
-            const int32_t st = dom ? ACX_MBFS_DOMAIN : ACX_MBFS_OVERFLOW;
-            a.status[q] = st;
-            a.nodes[q] = 0;
-            a.parents[q] = 0;
-            a.min_length[q] = 0;
-            a.path_len[q] = 0;
-            a.res[q] = Res{st, 0, 0, 0, 0, 0};
-        }
-        return;
-    }
+    const batch::Root root = batch::root_setup<GT, NW>(a, q, store, meta, table);
+    if (root.refused) return;
+    const int64_t max_nodes = root.max_nodes;
     if (lane == 0) {
-        const uint64_t lens = (uint64_t)s_n[0] | ((uint64_t)s_n[1] << 8);
-        const int bit = 4 * L;
-        rk[bit / 64] |= lens << (bit % 64);
-        if (bit % 64 > 48 && bit / 64 + 1 < kw) rk[bit / 64 + 1] |= lens >> (64 - bit % 64);
-    }
-    __syncthreads();
-    if (lane < kw) store[lane] = rk[lane];
-    if (lane == 0) {
-        const Key<NW + 1> key = kload<NW + 1>(rk, kw);
-        const uint64_t h = khash<NW + 1>(key, kw);
-        const Buckets tb{table, a.nb};
-        __hip_atomic_store(tb.bucket(tb.first(h)), visited::entry(a.ep, 0, visited::fp_of(h)), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_WORKGROUP);  // node 0
-        meta[0] = 0;
         depth[0] = 0;
-        hk[0] = prio_k0(rk, L, (int)total0, 0);
+        hk[0] = prio_k0(root.key, L, (int)root.total0, 0);
         hid[0] = 0;
     }
     __syncthreads();
@@ -253,7 +156,7 @@ __global__ __launch_bounds__(GT) void mgreedy_kernel(Args a) {
     int64_t n_nodes = 1, parents = 0, hn = 1;  // hn: entries of the heap
     int64_t end_node = 0;
     int32_t status = ACX_MBFS_OVERFLOW, last_act = 0, last_tot = 0;
-    uint32_t running = total0;
+    uint32_t running = root.total0;
 
     for (int64_t pop = 0; pop < a.rows; ++pop) {
         // take: the minimum leaves, the last entry sifts down from the root
@@ -361,10 +264,7 @@ __global__ __launch_bounds__(GT) void mgreedy_kernel(Args a) {
                 depth[pos] = dpar + 1;
                 hk[hpos] = myk;
                 hid[hpos] = (uint32_t)pos;
-                uint64_t* ent = table + slot[lane];
-                const uint64_t v = wload(ent);
-                __hip_atomic_store(ent, visited::entry_recode(v, (uint64_t)pos), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+                batch::recode_entry(table, slot[lane], (uint64_t)pos);
             }
         }
         running = min(running, wave_min((uint32_t)lane < seen_to ? tot : NONE));
@@ -437,139 +337,59 @@ __global__ __launch_bounds__(GT) void mgreedy_kernel(Args a) {
     }
 
     if (lane == 0) {
-        const bool path = status == ACX_BFS_EXHAUSTED || status == ACX_BFS_FOUND || status == ACX_BFS_BUDGET;
         // [(-1, total0)] + the edges to end_node + (last_act, last_tot)
-        a.status[q] = status;
-        a.nodes[q] = status < 0 ? 0 : n_nodes;
-        a.parents[q] = parents;
-        a.min_length[q] = (int32_t)running;
-        a.path_len[q] = path ? (int64_t)depth[end_node] + 2 : 0;
-        a.res[q] = Res{status, last_act, end_node, last_tot, 0, n_nodes};
+        batch::write_result(a, q, Res{status, last_act, end_node, last_tot, 0, n_nodes}, parents, running,
+                            batch::has_path(WITH_PATH, status) ? (int64_t)depth[end_node] + 2 : 0);
     }
 }
 
-// the reference's path of every search that returned one: thread per search, written at offsets[q]
-__global__ __launch_bounds__(TPB) void mgreedy_path_kernel(Args a, int64_t n, const int64_t* offsets, int32_t* actions,
-                                                           int32_t* totals, int64_t out_cap) {
-    const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (q >= n) return;
-    const Res r = a.res[q];
-    if (r.status != ACX_BFS_EXHAUSTED && r.status != ACX_BFS_FOUND && r.status != ACX_BFS_BUDGET) return;
-    if (r.end_node < 0 || r.end_node >= a.rows) return;
-    const uint64_t* store = a.store + q * a.rows * a.kw;
-    const uint32_t* meta = a.meta + q * a.rows;
-    const int64_t d = (a.depth + q * a.rows)[r.end_node];
-    const int64_t off = offsets[q];
-    if (off < 0 || off + d + 2 > out_cap) return;
-    actions[off] = -1;
-    totals[off] = key_total(store, a.L);
-    int64_t pos = off + d;
-    for (int64_t i = r.end_node; i != 0 && i < a.rows && pos > off; i = meta[i] >> 4, --pos) {
-        actions[pos] = (int32_t)(meta[i] & 15u);
-        totals[pos] = key_total(store + i * a.kw, a.L);
+// what the handle (acx_batch.h) needs of this engine
+struct Engine {
+    using Args = mgreedy::Args;
+    static constexpr uint32_t WITH_PATH = mgreedy::WITH_PATH;
+    static int64_t rows_for(int64_t B) { return B + OVERSHOOT; }
+    static uint32_t buckets_for(int64_t B) { return (uint32_t)((2 * (rows_for(B) + 12) + BUCKET - 1) / BUCKET); }
+    template <class F>
+    static void arrays(Args& a, F f) {
+        const size_t R = (size_t)a.rows;
+        f(a.store, 8 * (size_t)a.kw * R, false);
+        f(a.meta, 4 * R, false);
+        f(a.depth, 4 * R, false);
+        f(a.hk, 8 * R, false);
+        f(a.hid, 4 * R, false);
+        f(a.table, 8 * (size_t)BUCKET * a.nb, true);
+        f(a.res, sizeof(Res), true);
     }
-    actions[off + d + 1] = r.last_act;
-    totals[off + d + 1] = r.last_tot;
-}
-
-struct Batch {
-    int64_t n_cap = 0;
-    int epoch = 0;  // the last run's epoch (0: tables all zero)
-    size_t table_bytes = 0;
-    Args a{};
-
-    ~Batch() {
-        void* ptrs[] = {a.store, a.meta, a.depth, a.hk, a.hid, a.table, a.res};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-    }
-};
-
-struct RunLaunch {
-    Batch* S;
-    hipStream_t st;
-    int64_t n;
     template <int NW>
-    void go() { mgreedy_kernel<NW><<<dim3((unsigned)n), dim3(GT), 0, st>>>(S->a); }
+    static void launch(const Args& a, int64_t n, hipStream_t st) {
+        mgreedy_kernel<NW><<<dim3((unsigned)n), dim3(GT), 0, st>>>(a);
+    }
 };
 
 }  // namespace mgreedy
 }  // namespace acx
 
-using namespace acx::mgreedy;
+using acx::mgreedy::Engine;
+namespace batch = acx::batch;
 
 extern "C" {
 
-int64_t acx_mgreedy_bytes(int32_t L, int64_t max_nodes_each) {
-    if (L < 1 || L > ACX_MAX_L || max_nodes_each < 1 || max_nodes_each > MAX_NODES_EACH) return ACX_E_ARG;
-    const size_t kw = (size_t)acx_key_words(L), R = (size_t)rows_for(max_nodes_each);
-    return (int64_t)((8 * kw + 20) * R + (size_t)buckets_for(max_nodes_each) * BUCKET * 8 + sizeof(Res));
-}
+int64_t acx_mgreedy_bytes(int32_t L, int64_t max_nodes_each) { return batch::bytes<Engine>(L, max_nodes_each); }
 
 void* acx_mgreedy_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t cyclical) {
-    if (L < 1 || L > ACX_MAX_L || n_searches < 1 || n_searches > (1ll << 24) || max_nodes_each < 1 ||
-        max_nodes_each > MAX_NODES_EACH)
-        return nullptr;
-    Batch* S = new (std::nothrow) Batch();
-    if (!S) return nullptr;
-    Args& a = S->a;
-    a.L = L;
-    a.kw = acx_key_words(L);
-    a.cyc = cyclical != 0;
-    a.maxb = max_nodes_each;
-    a.rows = rows_for(max_nodes_each);
-    a.nb = buckets_for(max_nodes_each);
-    S->n_cap = n_searches;
-    const size_t n = (size_t)n_searches, R = (size_t)a.rows;
-    S->table_bytes = n * a.nb * BUCKET * 8;
-    bool ok = hipMalloc((void**)&a.store, n * R * a.kw * 8) == hipSuccess &&
-              hipMalloc((void**)&a.meta, n * R * 4) == hipSuccess &&
-              hipMalloc((void**)&a.depth, n * R * 4) == hipSuccess &&
-              hipMalloc((void**)&a.hk, n * R * 8) == hipSuccess &&
-              hipMalloc((void**)&a.hid, n * R * 4) == hipSuccess &&
-              hipMalloc((void**)&a.table, S->table_bytes) == hipSuccess &&
-              hipMalloc((void**)&a.res, n * sizeof(Res)) == hipSuccess &&
-              hipMemset(a.table, 0, S->table_bytes) == hipSuccess &&
-              hipMemset(a.res, 0, n * sizeof(Res)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete S;
-        return nullptr;
-    }
-    return S;
+    return batch::create<Engine>(L, n_searches, max_nodes_each, cyclical);
 }
 
-void acx_mgreedy_destroy(void* h) { delete static_cast<Batch*>(h); }
+void acx_mgreedy_destroy(void* h) { batch::destroy<Engine>(h); }
 
 int acx_mgreedy_run(void* h, const int32_t* states, const int64_t* budgets, int64_t n, int32_t* status, int64_t* nodes,
                     int64_t* parents, int32_t* min_length, int64_t* path_len, void* stream) {
-    Batch* S = static_cast<Batch*>(h);
-    if (!S || !states || !budgets || !status || !nodes || !parents || !min_length || !path_len) return ACX_E_ARG;
-    if (n < 0 || n > S->n_cap) return ACX_E_ARG;
-    if (n == 0) return ACX_OK;
-    hipStream_t st = (hipStream_t)stream;
-    Args& a = S->a;
-    if (!acx::visited::next_epoch(S->epoch, a.table, S->table_bytes, st, a.ep)) return ACX_E_LAUNCH;
-    a.states = states;
-    a.budgets = budgets;
-    a.status = status;
-    a.nodes = nodes;
-    a.parents = parents;
-    a.min_length = min_length;
-    a.path_len = path_len;
-    RunLaunch rl{S, st, n};
-    by_nw(a.L, rl);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return batch::run<Engine>(h, states, budgets, n, status, nodes, parents, min_length, path_len, stream);
 }
 
 int acx_mgreedy_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
                       void* stream) {
-    Batch* S = static_cast<Batch*>(h);
-    if (!S || !offsets || !actions || !totals || n < 0 || n > S->n_cap || cap < 0) return ACX_E_ARG;
-    if (n == 0) return ACX_OK;
-    mgreedy_path_kernel<<<dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream>>>(
-        S->a, n, offsets, actions, totals, cap);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return batch::paths<Engine>(h, n, offsets, actions, totals, cap, stream);
 }
 
 }  // extern "C"

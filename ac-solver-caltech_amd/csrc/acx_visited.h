@@ -7,7 +7,8 @@
 // so a search does not clear the table (it did: a 512 MB memset per 10^7-node search); the table
 // is cleared only when the 6-bit epoch wraps (next_epoch).
 //
-// acx_bfs.hip and acx_mbfs.hip insert with insert() below.  acx_greedy.hip shares the bucket and
+// acx_bfs.hip, acx_mbfs.hip and acx_mgreedy.hip insert with insert() below (the batched engines
+// through the table view of acx_batch.h).  acx_greedy.hip shares the bucket and
 // fingerprint format only: its entries are (id + 1) << 24 | fingerprint without an epoch, and
 // its read-only probe and CAS-only commit follow a protocol of their own (ids >= lo are skipped).
 #pragma once

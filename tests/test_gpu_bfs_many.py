@@ -6,30 +6,18 @@ against the one-search device engine acx.bfs(engine="device")."""
 import contextlib
 import functools
 import io
-import json
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
-
 import bfs_yardstick as Y
+from many_common import AK2, _check_records, _dataset_rows, _load, _norm, _same, _scrambled
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-
-
-def _load(name):
-    with open(os.path.join(GOLDEN, name)) as f:
-        return json.load(f)
-
-
-def _norm(r):
-    return None if r is None else [bool(r[0]), None if r[1] is None else [list(x) for x in r[1]]]
 
 
 def _many(pres, budgets, cyc=False, **kw):
@@ -50,15 +38,6 @@ def _device_engine(pres, budget, cyc=False):
         except AssertionError:
             res = None
     return res, dict(D.LAST_STATS)
-
-
-def _check_records(recs, res, st, nodes_key="nodes"):
-    for i, c in enumerate(recs):
-        assert res[i] == [c["ok"], c["path"]], (i, c)
-        if c[nodes_key] is not None:
-            assert st["status"][i] == Y.BUDGET and st["nodes"][i] == c[nodes_key], (i, c)
-        else:
-            assert st["status"][i] == (Y.FOUND if c["ok"] else Y.EXHAUSTED), (i, c)
 
 
 def test_dataset_part_in_one_call(capsys):
@@ -106,8 +85,7 @@ def test_random_reference_searches_grouped_by_length_and_flag():
 
 def test_kat_ak2_and_miller_schupp():
     kat = _load("kat_search.json")
-    ak2 = [1, 1, -2, -2, -2, 0, 0, 1, 2, 1, -2, -1, -2, 0]
-    res, st = _many(np.array([ak2, ak2]), [10 ** 6, 10])
+    res, st = _many(np.array([AK2, AK2]), [10 ** 6, 10])
     assert res == [kat["bfs_ak2"], [False, None]] and kat["bfs_ak2"][0]
     assert st["status"].tolist() == [Y.FOUND, Y.BUDGET]
     case = next(c for c in kat["miller_schupp"] if c["search_fn"] == "bfs")
@@ -142,22 +120,6 @@ def test_scale_records_at_L128_as_one_batch():
 # ---------------------------------------------------------------------------------------------
 BIG = 3000
 FLAGS = ("crosses_64", "mid_round_cut", "success_beats_cut", "cut_beats_success", "same_child_in_round")
-
-
-def _scrambled(L, rng, k):
-    """a trivial presentation after k oracle moves (no cyclic reduction), none leading back"""
-    from oracle import oracle as O
-    s = np.zeros(2 * L, np.int32)
-    s[0], s[L] = [(1, 2), (-2, 1), (2, -1), (-1, -2)][int(rng.integers(4))]
-    seen = {s.tobytes()}
-    for _ in range(k):
-        for _ in range(100):
-            out, _, err = O.move_batch(s[None], np.array([rng.integers(12)], np.int32), L, False)
-            if err[0] == 0 and out[0].tobytes() not in seen:
-                s = out[0].astype(np.int32)
-                seen.add(s.tobytes())
-                break
-    return s
 
 
 @functools.lru_cache(maxsize=None)
@@ -231,17 +193,6 @@ def test_round_boundaries_against_yardstick_and_device_engine(L):
 # ---------------------------------------------------------------------------------------------
 # batch shapes, splitting, workspace reuse
 # ---------------------------------------------------------------------------------------------
-def _dataset_rows():
-    import acx
-    rows = acx.data.load_initial_states("all")[::5].astype(np.int32)
-    assert rows.shape == (238, 36)
-    return rows
-
-
-def _same(a, b):
-    return a[0] == b[0] and all(np.array_equal(a[1][k], b[1][k]) for k in a[1])
-
-
 @pytest.mark.parametrize("N", [1, 3])
 def test_small_batches(N):
     rows = _dataset_rows()[:N]

@@ -5,7 +5,6 @@ reproduces the reference's own recorded runs -- tests/golden/greedy_many.json
 kat_search.json; the frontier order the kernel uses (csrc/acx_prio.h) is the host engines'
 priority-key order and the definition (tests/prio_check.cpp, built with the host compiler); the
 argument checks are made before any GPU call."""
-import json
 import os
 import subprocess
 
@@ -13,16 +12,13 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, PKG_ROOT, REPO
+from conftest import PKG_ROOT, REPO
 
 import greedy_yardstick as Y
+import many_common
+from many_common import _load
 
-AK2 = np.array([1, 1, -2, -2, -2, 0, 0, 1, 2, 1, -2, -1, -2, 0])
-
-
-def _load(name):
-    with open(os.path.join(GOLDEN, name)) as f:
-        return json.load(f)
+AK2 = np.array(many_common.AK2)
 
 
 def _check(c):

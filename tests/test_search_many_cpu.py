@@ -2,21 +2,12 @@
 the yardstick its GPU tests rest on (tests/bfs_yardstick.py, the reference's bfs restated over the
 oracle's expansion) reproduces the reference's own recorded runs -- tests/golden/search_many.json
 (make_search_many_golden.py) and the BFS records of kat_search_extra.json."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
-
 import bfs_yardstick as Y
-
-
-def _load(name):
-    with open(os.path.join(GOLDEN, name)) as f:
-        return json.load(f)
+from many_common import _load
 
 
 def _check(c):
