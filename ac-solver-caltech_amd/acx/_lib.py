@@ -21,6 +21,9 @@ BFS_EXHAUSTED, BFS_FOUND, BFS_BUDGET, BFS_MOVE_ERROR = 0, 1, 2, 3
 MBFS_DOMAIN, MBFS_OVERFLOW = -3, -4
 ERR_NONE, ERR_INVALID, ERR_EMPTY_CONJ, ERR_DOMAIN, ERR_ACTION, ERR_PAD = 0, 1, 2, 3, 4, 9
 MAX_L = 128
+# acx_rollout_deal (include/acx.h ACX_DEAL_*, ACX_ROLLOUT_DEAL_WORDS)
+DEAL_PLAIN, DEAL_XCC, DEAL_AUTO = 0, 1, 2
+DEAL_PCT, DEAL_OVER_PCT, ROLLOUT_DEAL_WORDS = 80, 125, 256
 
 # every entry point declared in include/acx.h, with its ctypes signature
 _P = ctypes.c_void_p
@@ -47,6 +50,9 @@ SIGNATURES = {
     "acx_pack_actions": ([_P, _P, _I32, _I64, _P], ctypes.c_int),
     "acx_rollout_packed": ([_P] * 10 + [_I32, _I64, _I32, _I32, _I32, _P], ctypes.c_int),
     "acx_rollout_obs8": ([_P] * 11 + [_I32, _I64, _I32, _I32, _I32, _P], ctypes.c_int),
+    # ..., T, B, L, horizon, cyclical, deal, pct, over_pct, deal_ws, stream
+    "acx_rollout_deal": ([_P] * 12 + [_I32, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P], ctypes.c_int),
+    "acx_rollout_deal_info": ([_I32, _I64, _I32, _I32, _I32, _I32, _I32, _P], ctypes.c_int),
     "acx_expand12": ([_P] * 6 + [_I64, _I32, _I32, _P], ctypes.c_int),
     "acx_canonicalize": ([_P] * 5 + [_I64, _I32, _I32, _P], ctypes.c_int),
     "acx_unpack_keys": ([_P] * 3 + [_I64, _I32, _P], ctypes.c_int),

@@ -6,6 +6,7 @@ torch stream and never synchronises.  Presentations are (B, 2L) int32 tensors.
 
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -197,6 +198,43 @@ def packs_actions(T: int, obs_traj: Optional[torch.Tensor]) -> bool:
     return obs_traj.dtype != torch.int8 and T > 32
 
 
+_DEALS = {None: _lib.DEAL_AUTO, "plain": _lib.DEAL_PLAIN, "xcc": _lib.DEAL_XCC}
+
+
+def _deal_mode(deal: Optional[str], pct: Optional[int], over_pct: Optional[int]):
+    if deal not in _DEALS:
+        raise ValueError(f"deal must be None, 'plain' or 'xcc', got {deal!r}")
+    pct = _lib.DEAL_PCT if pct is None else int(pct)
+    over_pct = _lib.DEAL_OVER_PCT if over_pct is None else int(over_pct)
+    if not 0 <= pct <= 100 or not 100 <= over_pct <= 400:
+        raise ValueError(f"deal_pct must be in [0, 100] and deal_over_pct in [100, 400], got {pct}, {over_pct}")
+    return _DEALS[deal], pct, over_pct
+
+
+def _deal_workspace(ws: Optional[torch.Tensor], dev) -> torch.Tensor:
+    """the XCC deal's range heads (acx_rollout_deal zeroes them on the launch's stream)"""
+    if ws is None:
+        return torch.empty(_lib.ROLLOUT_DEAL_WORDS, dtype=_INT32, device=dev)
+    if (ws.dtype != _INT32 or ws.device != dev or not ws.is_contiguous() or ws.numel() < _lib.ROLLOUT_DEAL_WORDS):
+        raise ValueError(f"deal_workspace must be a contiguous int32 tensor of >= {_lib.ROLLOUT_DEAL_WORDS} "
+                         f"elements on {dev}")
+    return ws
+
+
+def rollout_deal_info(T: int, B: int, L: int, obs_traj: Optional[torch.Tensor] = None, *,
+                      deal: Optional[str] = None, deal_pct: Optional[int] = None,
+                      deal_over_pct: Optional[int] = None) -> dict:
+    """acx_rollout_deal_info: how a rollout launch of these dimensions deals its blocks of 256 envs
+    on the current device -- `xcc` (the XCC deal is taken), `tiles` (blocks of the batch), `grid`
+    (workgroups launched), `resident` (workgroups of one resident round) and the 8 ranges' `quotas`."""
+    mode, pct, over = _deal_mode(deal, deal_pct, deal_over_pct)
+    kind = 0 if obs_traj is None else (2 if obs_traj.dtype == torch.int8 else 1)
+    info = (ctypes.c_int64 * 12)()
+    _lib.check(_lib.load().acx_rollout_deal_info(int(T), int(B), int(L), kind, mode, pct, over, info),
+               "acx_rollout_deal_info")
+    return {"xcc": bool(info[0]), "tiles": info[1], "grid": info[2], "resident": info[3], "quotas": list(info[4:12])}
+
+
 def rollout(
     state: torch.Tensor,
     actions: torch.Tensor,
@@ -213,6 +251,10 @@ def rollout(
     err_count: Optional[torch.Tensor] = None,
     pack_actions: Optional[bool] = None,
     packed_workspace: Optional[torch.Tensor] = None,
+    deal: Optional[str] = None,
+    deal_pct: Optional[int] = None,
+    deal_over_pct: Optional[int] = None,
+    deal_workspace: Optional[torch.Tensor] = None,
 ) -> None:
     """acx_rollout: T = actions.shape[0] fused env steps; state/step_count updated in place.
 
@@ -223,9 +265,17 @@ def rollout(
     Identical results either way; None (default) picks by `packs_actions` (T, obs dtype).
 
     obs_traj may be int32 or int8 (T, B, 2L): int8 is the reference's observation dtype
-    (ac_env.py:64-70) and goes to acx_rollout_obs8 (a quarter of the trajectory bytes)."""
+    (ac_env.py:64-70) and goes to acx_rollout_obs8 (a quarter of the trajectory bytes).
+
+    deal: how the launch deals its blocks of 256 envs to the XCDs (include/acx.h acx_rollout_deal).
+    "plain": block = workgroup index.  "xcc": by the XCC a workgroup runs on, an odd XCC's range
+    `deal_pct` % of an even one's, whatever is left stolen by the XCDs that run out, with a grid of
+    `deal_over_pct` % of the blocks.  None: "xcc" when the batch is more than one resident round and
+    T > 32, else "plain".  Identical results.  `deal_workspace`: the deal's heads
+    (_lib.ROLLOUT_DEAL_WORDS int32, allocated if not given; one per launch that may overlap)."""
     lib = _lib.load()
     T = actions.shape[0]
+    mode, pct, over = _deal_mode(deal, deal_pct, deal_over_pct)
     L, B, dev, obs8 = _check_rollout(state, reset_state, step_count, T, obs_traj, reward_traj, done_traj, trunc_traj,
                                      err, err_count)
     _check(actions, "actions", _INT32, (T, B), dev)
@@ -240,28 +290,31 @@ def rollout(
             raise ValueError(f"packed_workspace must be a contiguous int32 tensor of >= {words * B} elements on {dev}")
         st = lib.acx_pack_actions(_ptr(actions), _ptr(packed_workspace), T, B, _stream(dev))
         _lib.check(st, "acx_pack_actions")
-        if obs8:
-            st = lib.acx_rollout_obs8(
-                _ptr(state), None, _ptr(packed_workspace), _ptr(reset_state), _ptr(step_count), _ptr(obs_traj),
-                _ptr(reward_traj), _ptr(done_traj), _ptr(trunc_traj), _ptr(err), _ptr(err_count), T, B, L,
-                int(horizon), int(bool(cyclical)), _stream(dev),
-            )
-            _lib.check(st, "acx_rollout_obs8")
-            return
-        st = lib.acx_rollout_packed(
-            _ptr(state), _ptr(packed_workspace), _ptr(reset_state), _ptr(step_count), _ptr(obs_traj),
-            _ptr(reward_traj), _ptr(done_traj), _ptr(trunc_traj), _ptr(err), _ptr(err_count), T, B, L, int(horizon),
-            int(bool(cyclical)), _stream(dev),
+    ids = (None, _ptr(packed_workspace)) if pack_actions and T > 0 and B > 0 else (_ptr(actions), None)
+    if mode != _lib.DEAL_PLAIN and T > 0 and B > 0:
+        st = lib.acx_rollout_deal(
+            _ptr(state), *ids, _ptr(reset_state), _ptr(step_count), None if obs8 else _ptr(obs_traj),
+            _ptr(obs_traj) if obs8 else None, _ptr(reward_traj), _ptr(done_traj), _ptr(trunc_traj), _ptr(err),
+            _ptr(err_count), T, B, L, int(horizon), int(bool(cyclical)), mode, pct, over,
+            _ptr(_deal_workspace(deal_workspace, dev)), _stream(dev),
         )
-        _lib.check(st, "acx_rollout_packed")
+        _lib.check(st, "acx_rollout_deal")
         return
     if obs8:
         st = lib.acx_rollout_obs8(
-            _ptr(state), _ptr(actions), None, _ptr(reset_state), _ptr(step_count), _ptr(obs_traj), _ptr(reward_traj),
+            _ptr(state), *ids, _ptr(reset_state), _ptr(step_count), _ptr(obs_traj), _ptr(reward_traj),
             _ptr(done_traj), _ptr(trunc_traj), _ptr(err), _ptr(err_count), T, B, L, int(horizon),
             int(bool(cyclical)), _stream(dev),
         )
         _lib.check(st, "acx_rollout_obs8")
+        return
+    if ids[1] is not None:
+        st = lib.acx_rollout_packed(
+            _ptr(state), ids[1], _ptr(reset_state), _ptr(step_count), _ptr(obs_traj),
+            _ptr(reward_traj), _ptr(done_traj), _ptr(trunc_traj), _ptr(err), _ptr(err_count), T, B, L, int(horizon),
+            int(bool(cyclical)), _stream(dev),
+        )
+        _lib.check(st, "acx_rollout_packed")
         return
     st = lib.acx_rollout(
         _ptr(state), _ptr(actions), _ptr(reset_state), _ptr(step_count), _ptr(obs_traj), _ptr(reward_traj),
@@ -278,8 +331,10 @@ class RolloutPlan:
     (acx_pack_actions + acx_rollout_packed / acx_rollout_obs8, or acx_rollout /
     acx_rollout_obs8 on the int32 ids) on the current stream.  This is what a PPO loop that
     reuses its rollout storage every update calls; results are identical to ops.rollout with the
-    same arguments.  The plan keeps references to its tensors; their storage must not be
-    resized or replaced."""
+    same arguments.  `deal`, `deal_pct`, `deal_over_pct` as ops.rollout; which deal the launches
+    take is `plan.deal` ("plain" or "xcc") and `plan.deal_info` (rollout_deal_info), and a plan that
+    takes the XCC deal owns its heads.  The plan keeps references to its tensors; their storage
+    must not be resized or replaced."""
 
     def __init__(
         self,
@@ -297,6 +352,9 @@ class RolloutPlan:
         err: Optional[torch.Tensor] = None,
         err_count: Optional[torch.Tensor] = None,
         pack_actions: Optional[bool] = None,
+        deal: Optional[str] = None,
+        deal_pct: Optional[int] = None,
+        deal_over_pct: Optional[int] = None,
     ):
         lib = _lib.load()
         T = int(T)
@@ -311,7 +369,26 @@ class RolloutPlan:
         tail = (_ptr(reset_state), _ptr(step_count), _ptr(obs_traj), _ptr(reward_traj), _ptr(done_traj),
                 _ptr(trunc_traj), _ptr(err), _ptr(err_count), T, B, L, int(horizon), int(bool(cyclical)))
         self._head = (_ptr(state),)
-        if self.packs:
+        # the deal is settled here too (`deal_info`): "plain" keeps the entries below; "xcc" goes to
+        # acx_rollout_deal with heads of the plan's own, so two plans never share them
+        _, pct, over = _deal_mode(deal, deal_pct, deal_over_pct)
+        with torch.cuda.device(dev):  # the resident round is asked of the plan's device
+            self.deal_info = rollout_deal_info(T, B, L, obs_traj, deal=deal, deal_pct=pct, deal_over_pct=over)
+        self.deal = "xcc" if self.deal_info["xcc"] else "plain"
+        if self.deal == "xcc" and T > 0 and B > 0:
+            self._deal_ws = _deal_workspace(None, dev)
+            self._fn, self._name = lib.acx_rollout_deal, "acx_rollout_deal"
+            obs = (None, _ptr(obs_traj)) if obs8 else (_ptr(obs_traj), None)
+            self._tail = ((_ptr(reset_state), _ptr(step_count)) + obs + tail[3:]
+                          + (_lib.DEAL_XCC, pct, over, self._deal_ws.data_ptr()))
+            if self.packs:
+                self._ws = torch.empty(((T + 7) // 8, B), dtype=_INT32, device=dev)
+                self._wsp = self._ws.data_ptr()
+                self._pack = lib.acx_pack_actions
+                self._args = (_ptr(state), None, self._wsp) + self._tail
+            else:
+                self._tail = (None,) + self._tail
+        elif self.packs:
             self._ws = torch.empty(((T + 7) // 8, B), dtype=_INT32, device=dev)
             self._wsp = self._ws.data_ptr()
             self._pack = lib.acx_pack_actions

@@ -405,6 +405,42 @@ int acx_rollout_obs8(int32_t* state, const int32_t* actions, const uint32_t* pac
     return dispatch(L, f);
 }
 
+static bool deal_ok(int32_t deal, int32_t pct, int32_t over_pct) {
+    return deal >= ACX_DEAL_PLAIN && deal <= ACX_DEAL_AUTO && pct >= 0 && pct <= 100 && over_pct >= 100 &&
+           over_pct <= 400;
+}
+
+int acx_rollout_deal(int32_t* state, const int32_t* actions, const uint32_t* packed_actions, const int32_t* reset_state,
+                     int32_t* step_count, int32_t* obs_traj, int8_t* obs_traj8, int32_t* reward_traj,
+                     uint8_t* done_traj, uint8_t* trunc_traj, uint8_t* err, int32_t* err_count, int32_t T, int64_t B,
+                     int32_t L, int32_t horizon, int32_t cyclical, int32_t deal, int32_t pct, int32_t over_pct,
+                     uint32_t* deal_ws, void* stream) {
+    if (!deal_ok(deal, pct, over_pct)) return ACX_E_ARG;
+    RolloutArgs a{};
+    const int rc = rollout_args(a, state, actions, packed_actions, reset_state, step_count, obs_traj, obs_traj8,
+                                reward_traj, done_traj, trunc_traj, err, err_count, T, B, L, horizon, cyclical);
+    if (rc != ACX_OK || B == 0 || T == 0) return rc;
+    if ((!actions == !packed_actions) || (obs_traj && obs_traj8)) return ACX_E_ARG;
+    if (deal != ACX_DEAL_PLAIN && (!deal_ws || ((uintptr_t)deal_ws & 3u))) return ACX_E_ARG;
+    RolloutLaunch f{a, (hipStream_t)stream, DealRequest{deal, pct, over_pct, deal_ws, nullptr}};
+    return dispatch(L, f);
+}
+
+int acx_rollout_deal_info(int32_t T, int64_t B, int32_t L, int32_t obs_kind, int32_t deal, int32_t pct,
+                          int32_t over_pct, int64_t* info) {
+    if (!dims_ok(B, L) || T < 0 || obs_kind < 0 || obs_kind > 2 || !deal_ok(deal, pct, over_pct) || !info)
+        return ACX_E_ARG;
+    // only which kernel and how many blocks matter here: the trajectory pointers pick the kernel
+    RolloutArgs a{};
+    a.B = B;
+    a.T = T;
+    a.L = L;
+    a.obs_traj = obs_kind == 1 ? reinterpret_cast<int32_t*>(info) : nullptr;
+    a.obs_traj8 = obs_kind == 2 ? reinterpret_cast<int8_t*>(info) : nullptr;
+    RolloutLaunch f{a, nullptr, DealRequest{deal, pct, over_pct, nullptr, info}};
+    return dispatch(L, f);
+}
+
 int acx_expand12(const int32_t* parents, int32_t* children, int32_t* child_len, uint64_t* child_key, uint8_t* err,
                  int32_t* err_count, int64_t N, int32_t L, int32_t cyclical, void* stream) {
     if (!dims_ok(N, L)) return ACX_E_ARG;

@@ -81,10 +81,74 @@ int launch_step(StepArgs a, hipStream_t s) {
     step_kernel<NW, LC, VEC, LEARN><<<dim3(grid_for(a.B)), dim3(BLOCK), shm, s>>>(a);
     return finish_launch();
 }
+// How a rollout launch deals its blocks (acx_rollout_deal).  mode ACX_DEAL_*; pct: an odd XCC's
+// range as a percentage of an even one's; over_pct: the grid as a percentage of the blocks (the
+// surplus is what a fast XCD steals with); ws: the caller's ACX_ROLLOUT_DEAL_WORDS head counters.
+// info (acx_rollout_deal_info): filled instead of launching.
+struct DealRequest {
+    int mode = ACX_DEAL_PLAIN, pct = ACX_DEAL_PCT, over_pct = ACX_DEAL_OVER_PCT;
+    uint32_t* ws = nullptr;
+    int64_t* info = nullptr;
+};
+// Launches of at most this many steps (the ones that read int32 ids) keep the plain deal under
+// ACX_DEAL_AUTO: at K = 20 the deal's medians were 1.312-1.326 ms against the plain launch's 1.302
+// (profiles/r07/r07a_ab_deal_sweep.json, DESIGN.md "Rollout")
+constexpr int DEAL_AUTO_MIN_T = 32;
+
+// range limits for `tiles` blocks: the even XCCs weigh 100, the odd ones pct
+static inline void deal_bounds(int64_t tiles, int pct, uint32_t* bound) {
+    const int64_t total = 4 * (100 + (int64_t)pct);
+    for (int x = 0; x <= (int)XCC_RANGES; ++x) {
+        const int64_t before = (int64_t)((x + 1) / 2) * 100 + (int64_t)(x / 2) * pct;  // weights of XCCs < x
+        bound[x] = (uint32_t)(tiles * before / total);
+    }
+}
+
 template <int NW, int LC, int VEC, int OBS>
-int launch_rollout(RolloutArgs a, hipStream_t s) {
+int launch_rollout(RolloutArgs a, hipStream_t s, DealRequest d) {
     const size_t shm = smem_bytes<NW, LC, VEC>(a.L);
-    rollout_kernel<NW, LC, VEC, OBS><<<dim3(grid_for(a.B)), dim3(BLOCK), shm, s>>>(a);
+    unsigned grid = grid_for(a.B);
+    a.deal = XccDeal{};
+    if (d.mode != ACX_DEAL_PLAIN || d.info) {
+        const int64_t tiles = grid;
+        const int64_t dealt_grid = 8 * ((tiles * d.over_pct + 799) / 800);
+        bool on = d.mode == ACX_DEAL_XCC;
+        int64_t resident = 0;
+        if (d.mode == ACX_DEAL_AUTO || d.info) {
+            // one resident round: blocks per CU (the occupancy query) x CUs of the current device
+            int dev = 0, cus = 0, per_cu = 0;
+            if (hipGetDevice(&dev) != hipSuccess ||
+                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_kernel<NW, LC, VEC, OBS>, BLOCK, shm) !=
+                    hipSuccess)
+                return ACX_E_LAUNCH;
+            resident = (int64_t)per_cu * cus;
+            if (d.mode == ACX_DEAL_AUTO) on = tiles > resident && a.T > DEAL_AUTO_MIN_T;
+        }
+        if (dealt_grid > INT32_MAX) {
+            if (d.mode == ACX_DEAL_XCC) return ACX_E_ARG;
+            on = false;
+        }
+        if (on) {
+            deal_bounds(tiles, d.pct, a.deal.bound);
+            a.deal.heads = d.ws;
+            grid = (unsigned)dealt_grid;
+        }
+        if (d.info) {
+            d.info[0] = on;
+            d.info[1] = tiles;
+            d.info[2] = grid;
+            d.info[3] = resident;
+            if (!on) deal_bounds(tiles, d.pct, a.deal.bound);
+            for (int x = 0; x < (int)XCC_RANGES; ++x) d.info[4 + x] = a.deal.bound[x + 1] - a.deal.bound[x];
+            return ACX_OK;
+        }
+        if (on) {
+            if (!d.ws) return ACX_E_ARG;
+            if (hipMemsetAsync(d.ws, 0, ACX_ROLLOUT_DEAL_WORDS * sizeof(uint32_t), s) != hipSuccess) return ACX_E_LAUNCH;
+        }
+    }
+    rollout_kernel<NW, LC, VEC, OBS><<<dim3(grid), dim3(BLOCK), shm, s>>>(a);
     return finish_launch();
 }
 template <int NW, int LC, int VEC>
@@ -130,7 +194,7 @@ int launch_unpack(UnpackArgs a, hipStream_t s) {
 #define ACX_INST_STEP(EXT, NW, LC, VEC)                                   \
     EXT template int launch_step<NW, LC, VEC, false>(StepArgs, hipStream_t); \
     EXT template int launch_step<NW, LC, VEC, true>(StepArgs, hipStream_t);
-#define ACX_INST_ROLL(EXT, NW, LC, VEC, OBS) EXT template int launch_rollout<NW, LC, VEC, OBS>(RolloutArgs, hipStream_t);
+#define ACX_INST_ROLL(EXT, NW, LC, VEC, OBS) EXT template int launch_rollout<NW, LC, VEC, OBS>(RolloutArgs, hipStream_t, DealRequest);
 #define ACX_INST_SEARCH(EXT, NW, LC, VEC)                                 \
     EXT template int launch_expand<NW, LC, VEC>(ExpandArgs, hipStream_t);  \
     EXT template int launch_canon<NW, LC, VEC>(CanonArgs, hipStream_t);    \
@@ -201,11 +265,12 @@ struct StepLaunch {
 struct RolloutLaunch {
     RolloutArgs a;
     hipStream_t s;
+    DealRequest d;
     template <int NW, int LC, int VEC>
     int go() {
-        if (a.obs_traj8) return launch_rollout<NW, LC, VEC, 2>(a, s);
-        if (a.obs_traj) return launch_rollout<NW, LC, VEC, 1>(a, s);
-        return launch_rollout<NW, LC, VEC, 0>(a, s);
+        if (a.obs_traj8) return launch_rollout<NW, LC, VEC, 2>(a, s, d);
+        if (a.obs_traj) return launch_rollout<NW, LC, VEC, 1>(a, s, d);
+        return launch_rollout<NW, LC, VEC, 0>(a, s, d);
     }
 };
 struct ExpandLaunch {

@@ -18,7 +18,14 @@ __global__ __launch_bounds__(BLOCK, Occupancy<LC>::waves_per_simd) void rollout_
     using Tile = TileFor<NW, LC, VEC>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     WaveCtx w;
-    if (!wave_ctx(a.B, w)) return;
+    // which block of 256 envs: blockIdx, or (a.deal.heads) the one dealt by XCC -- the store-bound
+    // launch ends when the slowest XCD has stored its share, so the shares follow the XCDs' rates
+    int64_t blk = (int64_t)blockIdx.x;
+    if (a.deal.heads) {
+        blk = xcc_deal_block(a.deal, smem);
+        if (blk < 0) return;
+    }
+    if (!wave_ctx_at(a.B, blk, w)) return;
     Tile tile(smem + w.wid * Tile::wave_bytes(a.L), a.L);
     const int L = tile.Lr(), twoL = 2 * L;
     const int64_t env = w.r0 + w.lane;

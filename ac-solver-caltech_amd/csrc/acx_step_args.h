@@ -60,6 +60,18 @@ struct StepArgs {
     uint8_t* reduced;
 };
 
+// The rollout's XCC deal (acx_kernel_common.h xcc_deal_block; filled by launch_rollout).  heads NULL:
+// the plain deal, block = blockIdx.  heads: the caller's workspace (ACX_ROLLOUT_DEAL_WORDS uint32,
+// zeroed on the launch's stream before the kernel), range x's head counter at word
+// x * XCC_HEAD_STRIDE -- a cache line each, so the XCDs' atomics do not queue on one line.
+// bound: the ranges' limits, bound[0] = 0 <= ... <= bound[8] = blocks of the batch.
+constexpr uint32_t XCC_RANGES = 8;
+constexpr uint32_t XCC_HEAD_STRIDE = 32;
+struct XccDeal {
+    uint32_t* heads;
+    uint32_t bound[XCC_RANGES + 1];
+};
+
 struct RolloutArgs {
     int32_t* state;
     const int32_t* actions;
@@ -75,6 +87,7 @@ struct RolloutArgs {
     int64_t B;
     int T, L, horizon, cyclical;
     int8_t* obs_traj8;  // acx_rollout_obs8: the trajectory as int8 letters (obs_traj unused)
+    XccDeal deal;       // acx_rollout_deal (heads NULL: block = blockIdx)
 };
 
 struct ExpandArgs {

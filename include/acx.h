@@ -307,6 +307,44 @@ int acx_rollout_obs8(int32_t* state, const int32_t* actions, const uint32_t* pac
                      int64_t B, int32_t L, int32_t horizon, int32_t cyclical, void* stream);
 
 /*
+ * Any of the three rollouts above with a choice of how the launch deals its blocks of 256 envs to
+ * the GPU's XCDs.  The rollout is bound by its trajectory stores and the XCDs do not store equally
+ * fast, so a launch that gives every XCD the same number of blocks ends with the fast ones idle.
+ *   ACX_DEAL_PLAIN  block = workgroup index (what acx_rollout, _packed and _obs8 do)
+ *   ACX_DEAL_XCC    the blocks are split into 8 contiguous ranges, an odd XCC's `pct` % of an even
+ *                   one's; a workgroup reads the XCC it runs on, takes the next block of that
+ *                   XCC's range and, when the range is exhausted, of the other ranges in turn.  The
+ *                   grid is `over_pct` % of the blocks, rounded up to a multiple of 8.  Every block
+ *                   is run exactly once whatever ids the hardware reports; results are identical.
+ *   ACX_DEAL_AUTO   ACX_DEAL_XCC when the batch is more than one resident round of the kernel
+ *                   (blocks per CU from the occupancy query x CUs) and T > 32, else ACX_DEAL_PLAIN
+ * pct in [0, 100] (ACX_DEAL_PCT), over_pct in [100, 400] (ACX_DEAL_OVER_PCT).  deal_ws: the range
+ * heads, ACX_ROLLOUT_DEAL_WORDS uint32 of device memory owned by the caller (not NULL unless
+ * ACX_DEAL_PLAIN); the launch zeroes it on `stream` before the kernel, so launches that may overlap
+ * (other streams, other GPUs) need a workspace each.  Exactly one of actions / packed_actions
+ * and at most one of obs_traj / obs_traj8 is given; everything else as acx_rollout.
+ */
+#define ACX_DEAL_PLAIN 0
+#define ACX_DEAL_XCC 1
+#define ACX_DEAL_AUTO 2
+/* chosen by the interleaved sweep profiles/r07/r07a_ab_deal_sweep.json (80 / 85 / 90 x 115 / 125 / 140) */
+#define ACX_DEAL_PCT 80
+#define ACX_DEAL_OVER_PCT 125
+#define ACX_ROLLOUT_DEAL_WORDS 256
+int acx_rollout_deal(int32_t* state, const int32_t* actions, const uint32_t* packed_actions,
+                     const int32_t* reset_state, int32_t* step_count, int32_t* obs_traj, int8_t* obs_traj8,
+                     int32_t* reward_traj, uint8_t* done_traj, uint8_t* trunc_traj, uint8_t* err,
+                     int32_t* err_count, int32_t T, int64_t B, int32_t L, int32_t horizon, int32_t cyclical,
+                     int32_t deal, int32_t pct, int32_t over_pct, uint32_t* deal_ws, void* stream);
+/*
+ * What acx_rollout_deal would do for these arguments on the current device, without launching
+ * (obs_kind 0 no trajectory, 1 int32, 2 int8): info[0] 1 if the XCC deal is taken, [1] blocks of the
+ * batch, [2] workgroups launched, [3] workgroups of one resident round, [4..11] the 8 ranges' sizes.
+ */
+int acx_rollout_deal_info(int32_t T, int64_t B, int32_t L, int32_t obs_kind, int32_t deal, int32_t pct,
+                          int32_t over_pct, int64_t* info);
+
+/*
  * 12-way neighbour expansion: for every parent (N,2L) and every move id a in [0,12)
  * the child ACMove(a, parent, L, cyclical) (greedy/bfs call it with cyclical=0).
  *   children   (N,12,2L) int32 or NULL

@@ -156,6 +156,59 @@ __global__ __launch_bounds__(256) void tile_ticket(int4* __restrict__ dst, int64
     }
 }
 
+// The rollout's XCC deal (csrc/acx_kernel_common.h xcc_deal_block) on the store pattern: the tiles
+// are 8 contiguous ranges [bound[x], bound[x + 1]), a block takes the next tile of the range of
+// the XCC it runs on (read from the hardware, not from blockIdx) and, when that is exhausted, of
+// the other ranges in turn from x + 1; a block that finds all eight exhausted exits.  heads: 8
+// counters, 32 words apart, zeroed by the host before the launch.  rec per tile; rec[2] = the XCC
+// that ran it | (1 << 8 if the tile was stolen from another XCC's range).
+struct DealBounds {
+    unsigned bound[9];
+};
+__global__ __launch_bounds__(256) void tile_deal(int4* __restrict__ dst, int64_t rows, int cpr, int K, DealBounds b,
+                                                 unsigned* __restrict__ heads, uint64_t* __restrict__ rec,
+                                                 uint64_t* __restrict__ steps) {
+    __shared__ int s_tile[2];
+    const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (threadIdx.x == 0) {
+        const unsigned x = xcc_id();
+        int tile = -1, stolen = 0;
+        for (unsigned i = 0; i < 8; ++i) {
+            const unsigned y = (x + i) & 7;
+            const unsigned quota = b.bound[y + 1] - b.bound[y];
+            if (quota == 0) continue;
+            const unsigned k = atomicAdd(heads + y * 32, 1u);
+            if (k < quota) {
+                tile = (int)(b.bound[y] + k);
+                stolen = i != 0;
+                break;
+            }
+        }
+        s_tile[0] = tile;
+        s_tile[1] = stolen;
+    }
+    __syncthreads();
+    const int tile = s_tile[0];
+    const int nch = WAVE * cpr;
+    if (tile >= 0) {
+        const int64_t r0 = ((int64_t)tile * 4 + wid) * WAVE;
+        for (int t = 0; t < K; ++t) {
+            if (wid == 0 && lane == 0) steps[(int64_t)tile * K + t] = __builtin_amdgcn_s_memrealtime();
+            int4* row = dst + ((int64_t)t * rows + r0) * cpr;
+            for (int c = lane; c < nch; c += WAVE) st_nt(row + c, make_int4(7, t, c, lane));
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+    if (threadIdx.x == 0 && tile >= 0) {
+        rec[4 * tile + 0] = t_start;
+        rec[4 * tile + 1] = __builtin_amdgcn_s_memrealtime();
+        rec[4 * tile + 2] = xcc_id() | ((uint64_t)s_tile[1] << 8);
+        rec[4 * tile + 3] = 1;
+    }
+}
+
 // One block per tile (kind 0), but a wave's issue priority falls with its progress (s_setprio
 // 3 at the start, 0 in its last quarter of steps): the arbiter serves the waves that are behind
 // first instead of the oldest, so a SIMD's waves advance together
@@ -198,7 +251,8 @@ __global__ __launch_bounds__(256) void tile_fair(int4* __restrict__ dst, int64_t
 
 // kind 0: one block per tile (the rollout's launch); 1: persistent blocks, dynamic tiles;
 // 2: persistent blocks, static tiles; 3: one block per tile, odd XCCs dealt grid/100 % of an even
-// XCC's tiles (grid = that percentage here).  grid: persistent blocks (rec / steps sized for the larger)
+// XCC's tiles (grid = that percentage here); 6: the rollout's XCC deal, weighted ranges with stealing
+// (tile_deal).  grid: persistent blocks (rec / steps sized for the larger)
 extern "C" int timeline_tile(int kind, void* buf, int64_t rows, int L, int K, int grid, void* ctr, void* rec,
                              void* steps, void* stream) {
     if (rows % 256 || K < 1 || grid < 1) return -1;
@@ -210,6 +264,18 @@ extern "C" int timeline_tile(int kind, void* buf, int64_t rows, int L, int K, in
     } else if (kind == 5) {
         tile_fair<<<dim3((unsigned)(rows / 256)), dim3(256), 0, s>>>((int4*)buf, rows, cpr, K, grid, (uint64_t*)rec,
                                                                      (uint64_t*)steps);
+    } else if (kind == 6) {
+        // grid = 1000 * over_pct + odd_pct: the rollout's deal (acx_launch.h deal_bounds and its grid);
+        // ctr: 256 words
+        const int64_t tiles = rows / 256;
+        const int pct = grid % 1000, over = grid / 1000;
+        if (pct > 100 || over < 100) return -3;
+        DealBounds b;
+        for (int x = 0; x <= 8; ++x)
+            b.bound[x] = (unsigned)(tiles * ((int64_t)((x + 1) / 2) * 100 + (int64_t)(x / 2) * pct) / (4 * (100 + pct)));
+        if (hipMemsetAsync(ctr, 0, 256 * sizeof(unsigned), s) != hipSuccess) return -2;
+        tile_deal<<<dim3((unsigned)(8 * ((tiles * over + 799) / 800))), dim3(256), 0, s>>>(
+            (int4*)buf, rows, cpr, K, b, (unsigned*)ctr, (uint64_t*)rec, (uint64_t*)steps);
     } else if (kind == 4) {
         const unsigned tiles = (unsigned)(rows / 256);
         tile_ticket<<<dim3((unsigned)((uint64_t)tiles * grid / 100)), dim3(256), 0, s>>>(

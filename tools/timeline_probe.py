@@ -36,7 +36,8 @@ def q(x, ps=(0, 10, 50, 90, 100)):
 
 
 def analyse(rec, steps, K, ev_ms, kind):
-    st, en, xcc = rec[:, 0].astype(np.float64), rec[:, 1].astype(np.float64), rec[:, 2]
+    st, en, xcc = rec[:, 0].astype(np.float64), rec[:, 1].astype(np.float64), rec[:, 2] & 0xff
+    stolen = (rec[:, 2] >> 8) & 1  # kind 6: the tile came from another XCC's range
     ntile = rec[:, 3]
     t0 = st.min()
     st, en = (st - t0) / 100.0, (en - t0) / 100.0  # 100 MHz clock -> us
@@ -67,12 +68,18 @@ def analyse(rec, steps, K, ev_ms, kind):
                            "median_duration_us": round(float(np.median((en - st)[xcc == x])), 1),
                            "tiles": int(ntile[xcc == x].sum()) if kind else int((xcc == x).sum())}
                   for x in np.unique(xcc)}
+    if kind == 6:
+        for x in res["xcc"]:
+            res["xcc"][x]["tiles_stolen"] = int(stolen[xcc == x].sum())
+        res["tiles_stolen"] = int(stolen.sum())
+    ends = [v["max_end_us"] for v in res["xcc"].values()]
+    res["xcc_end_spread_us"] = round(max(ends) - min(ends), 1)
     res["xcc_equals_block_mod_8"] = bool(np.all(xcc == (np.arange(nb) % 8)))
     return res
 
 
 KINDS = ["block_per_tile", "persistent_dynamic", "persistent_static", "block_per_tile_xcc_weighted", "block_per_ticket",
-         "block_per_tile_prio"]
+         "block_per_tile_prio", "block_per_tile_xcc_weighted_steal"]
 
 
 def main():
@@ -83,6 +90,8 @@ def main():
     ap.add_argument("--per-cu", default="8", help="persistent blocks per CU (4 waves each), comma-separated")
     ap.add_argument("--odd-pct", default="100,78", help="kind 3: an odd XCC's tiles as a percentage of an even one's")
     ap.add_argument("--over", default="100,125", help="kind 4: blocks launched as a percentage of the tiles")
+    ap.add_argument("--deal", default="80:125,100:125",
+                    help="kind 6: ODD_PCT:OVER_PCT pairs (the rollout's XCC deal: weighted ranges, stealing)")
     ap.add_argument("--prio", default="1,2,3", help="kind 5: priority modes (1 by progress, 2 young first, 3 fixed)")
     a = ap.parse_args()
     P = lib()
@@ -90,15 +99,16 @@ def main():
     B, L = 1 << 20, 36
     out = []
     ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-    ctr = torch.zeros(4, dtype=torch.int32, device=dev)
+    ctr = torch.zeros(256, dtype=torch.int32, device=dev)
     for K in [int(k) for k in a.K.split(",")]:
         obs = torch.zeros((K, B, 2 * L), dtype=torch.int32, device=dev)
         s = torch.cuda.current_stream().cuda_stream
         runs = [(int(k), int(p)) for k in a.kinds.split(",")
-                for p in ({"0": ["8"], "3": a.odd_pct.split(","), "4": a.over.split(","), "5": a.prio.split(",")}.get(k) or a.per_cu.split(","))]
+                for p in ({"0": ["8"], "3": a.odd_pct.split(","), "4": a.over.split(","), "5": a.prio.split(","),
+                          "6": [str(1000 * int(d.split(":")[1]) + int(d.split(":")[0])) for d in a.deal.split(",")]}.get(k) or a.per_cu.split(","))]
         for kind, per_cu in runs:
             grid = ncu * per_cu if kind in (1, 2) else per_cu  # persistent: per_cu waves per SIMD; else the kind's parameter
-            nb = B // 256 if kind in (0, 3, 4, 5) else grid
+            nb = B // 256 if kind in (0, 3, 4, 5, 6) else grid
             rec = torch.zeros((nb, 4), dtype=torch.int64, device=dev)
             steps = torch.zeros((nb, K), dtype=torch.int64, device=dev)
             ms = []
