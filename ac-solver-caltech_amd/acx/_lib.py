@@ -108,6 +108,9 @@ SIGNATURES = {
     "acx_sbfs_lookup": ([_P, _I64, _P, _P], ctypes.c_int),
     "acx_sbfs_trace": ([_P, _I64, _I64, _P, _I64, _P], ctypes.c_int64),
     "acx_sbfs_node_keys": ([_P, _P, _P, _I64, _P], ctypes.c_int64),
+    # the hash seam of the search engines (csrc/acx_test_hash.h; tests only)
+    "acx_internal_hash_classes": ([], ctypes.c_int32),
+    "acx_internal_key_hash": ([_P, _I32], ctypes.c_uint64),
 }
 
 # the batched engines, one workgroup per search: BFS (ac-solver-caltech_amd/csrc/acx_mbfs.hip) and

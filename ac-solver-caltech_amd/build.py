@@ -25,6 +25,13 @@ SOURCES = ["acx_kernels.hip", "acx_bfs.hip", "acx_mbfs.hip", "acx_mgreedy.hip", 
 # and its "extern template" block in acx_launch.h), in parallel: the runtime-L generic sets took
 # ~7 minutes in one object
 KERNEL_PARTS = 10
+# libacx_weakhash.so, next to libacx.so: the search units recompiled with the hash seam of
+# csrc/acx_test_hash.h at WEAK_CLASSES classes (objects in build/weakhash/), linked with the shipped
+# objects of every other unit.  Tests load it through $ACX_LIB (tests/test_weak_hash_cpu.py,
+# tests/test_gpu_weak_hash.py); nothing else does.
+WEAK_OUT = os.path.join(HERE, "acx", "libacx_weakhash.so")
+WEAK_SOURCES = ["acx_bfs.hip", "acx_mbfs.hip", "acx_mgreedy.hip", "acx_sbfs.hip", "acx_greedy.hip", "acx_search.cpp"]
+WEAK_CLASSES = 8
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ACX_OFFLOAD_ARCH", "gfx950")
 
@@ -63,6 +70,7 @@ def source_hash() -> str:
 
 MARK = b"acx-src-sha256:"
 STAMP = OUT + ".stamp"  # sidecar: the hash the library next to it was built with (written after the link)
+WEAK_STAMP = WEAK_OUT + ".stamp"
 
 
 def built_hash(path: str = OUT):
@@ -86,15 +94,16 @@ def built_hash(path: str = OUT):
             tail = data[-(len(MARK) + 64):]
 
 
-def _stale(digest: str) -> bool:
-    """the library is up to date when its sidecar stamp (or, without one, its embedded hash)
+def _stale(digest: str, out: str = OUT) -> bool:
+    """a library is up to date when its sidecar stamp (or, without one, its embedded hash)
     matches `digest`"""
-    if not os.path.exists(OUT):
+    stamp = out + ".stamp"
+    if not os.path.exists(out):
         return True
-    if os.path.exists(STAMP) and os.path.getmtime(STAMP) >= os.path.getmtime(OUT):
-        with open(STAMP) as f:
+    if os.path.exists(stamp) and os.path.getmtime(stamp) >= os.path.getmtime(out):
+        with open(stamp) as f:
             return f.read().strip() != digest
-    return built_hash() != digest
+    return built_hash(out) != digest
 
 
 def _obj_stamp(obj: str) -> str:
@@ -103,18 +112,22 @@ def _obj_stamp(obj: str) -> str:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     digest = source_hash()
-    if not force and not _stale(digest):
+    if not force and not _stale(digest) and not _stale(digest, WEAK_OUT):
         return OUT
     tc = toolchain_id()
-    objs = []
-    os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
+    objs, weak_objs = [], []
+    os.makedirs(os.path.join(HERE, "build", "weakhash"), exist_ok=True)
     procs = []
     headers = [os.path.join(INCLUDE, "acx.h")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC)
                                                    if f.endswith((".h", ".hpp"))]
-    units = [(src, None) for src in SOURCES] + [("acx_kernels.hip", n) for n in range(1, KERNEL_PARTS + 1)]
-    for src, part in units:
-        obj = os.path.join(HERE, "build", src + (f".p{part}" if part else "") + ".o")
-        objs.append(obj)
+    units = [(src, None, False) for src in SOURCES] + [("acx_kernels.hip", n, False) for n in range(1, KERNEL_PARTS + 1)]
+    units += [(src, None, True) for src in WEAK_SOURCES]
+    for src, part, weak in units:
+        obj = os.path.join(HERE, "build", "weakhash" if weak else "", src + (f".p{part}" if part else "") + ".o")
+        if weak:
+            weak_objs.append(obj)
+        else:
+            objs.append(obj)
         main_kernels = src == "acx_kernels.hip" and part is None  # carries the source hash: always rebuilt
         if not force and os.path.exists(obj) and not main_kernels and os.path.exists(_obj_stamp(obj)):
             t = os.path.getmtime(obj)
@@ -130,6 +143,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 cmd.insert(-3, f"-DACX_PART={part}")
         else:
             cmd = ["g++", *CXX_FLAGS, "-c", "-I", INCLUDE, os.path.join(CSRC, src), "-o", obj]
+        if weak:
+            cmd.insert(-3, f"-DACX_TEST_HASH_CLASSES={WEAK_CLASSES}")
         if verbose:
             print(" ".join(cmd))
         procs.append((obj, subprocess.Popen(cmd)))
@@ -138,12 +153,19 @@ def build(force: bool = False, verbose: bool = False) -> str:
             raise RuntimeError("libacx build failed")
         with open(_obj_stamp(obj), "w") as f:
             f.write(tc)
-    link = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", OUT] + objs
+    # the variant: its own objects of WEAK_SOURCES, the shipped objects of everything else
+    shipped = {os.path.basename(o) for o in weak_objs}
+    weak_objs += [o for o in objs if os.path.basename(o) not in shipped]
+    links = [subprocess.Popen([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out] + oo)
+             for out, oo in ((OUT, objs), (WEAK_OUT, weak_objs))]
     if verbose:
-        print(" ".join(link))
-    subprocess.check_call(link)
-    with open(STAMP, "w") as f:
-        f.write(digest)
+        for p in links:
+            print(" ".join(p.args))
+    if any([p.wait() != 0 for p in links]):
+        raise RuntimeError("libacx link failed")
+    for stamp in (STAMP, WEAK_STAMP):
+        with open(stamp, "w") as f:
+            f.write(digest)
     return OUT
 
 

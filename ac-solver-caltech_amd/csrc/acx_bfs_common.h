@@ -12,6 +12,7 @@
 #include "acx.h"
 #include "acx_key.h"
 #include "acx_moves.h"
+#include "acx_test_hash.h"
 
 namespace acx {
 namespace bfs {
@@ -59,7 +60,7 @@ __host__ __device__ __forceinline__ uint64_t khash(const Key<KWM>& k, int kw) {
 #pragma unroll
     for (int i = 0; i < KWM; ++i)
         if (i < kw) h = fmix64(h ^ k.w[i]) + 0x632be59bd9b4e019ull;
-    return fmix64(h);
+    return test_hash::finish(fmix64(h));  // the identity in the shipped build (acx_test_hash.h)
 }
 
 // n bytes (n % 4 == 0) device -> pinned host memory by a kernel (no DMA-engine copy: rocprofv3's

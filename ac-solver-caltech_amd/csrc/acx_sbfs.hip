@@ -928,6 +928,18 @@ int32_t acx_sbfs_owner(const int32_t* presentation, int32_t L, int32_t world) {
     return (int32_t)(((hv >> 32) * (uint64_t)world) >> 32);
 }
 
+// tests only: the hash seam's class count (0: the shipped hash) and the host value of khash
+int32_t acx_internal_hash_classes(void) { return acx::test_hash::CLASSES; }
+
+uint64_t acx_internal_key_hash(const uint64_t* key, int32_t L) {
+    if (!key || L < 1 || L > ACX_MAX_L) return 0;
+    constexpr int KM = ACX_MAX_L / 16 + 2;
+    const int kw = acx_key_words(L);
+    Key<KM> k{};
+    for (int i = 0; i < kw; ++i) k.w[i] = key[i];
+    return khash<KM>(k, kw);
+}
+
 int acx_sbfs_reset(void* h, const int32_t* presentation, void* stream) {
     Shard* S = static_cast<Shard*>(h);
     if (!S || !presentation) return ACX_E_ARG;

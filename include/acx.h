@@ -651,6 +651,17 @@ int32_t acx_key_words(int32_t L);
 /* library version string */
 const char* acx_version(void);
 
+/* ---- internal hooks (tests only) ----
+ * The search engines' key hashes end in one compile-time seam (csrc/acx_test_hash.h): a build
+ * with -DACX_TEST_HASH_CLASSES=K (libacx_weakhash.so) keeps K hash values, all of whose low 61
+ * bits are ones, so that every visited-set probe collides.
+ *   acx_internal_hash_classes  0 in the shipped library, K in such a build
+ *   acx_internal_key_hash      the hash the device engines' visited sets and the sbfs owner
+ *                              rule take of a packed key of L's key words (HOST pointer; the
+ *                              host value of bfs::khash); 0 on a bad argument */
+int32_t acx_internal_hash_classes(void);
+uint64_t acx_internal_key_hash(const uint64_t* key, int32_t L);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-"""Per-kernel VGPR / spill / SGPR / LDS figures from a built object's gfx950 code object.
+"""Per-kernel VGPR / SGPR (each with its spills) / LDS / scratch figures from a built object's gfx950 code object.
 
     python tools/kernel_resources.py [object.o] [name-substring ...]
 
@@ -35,7 +35,8 @@ def main():
             continue
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         print(f"vgpr {g('vgpr_count'):>4} spill {g('vgpr_spill_count'):>3} sgpr {g('sgpr_count'):>3} "
-              f"lds {g('group_segment_fixed_size'):>6}  {dem[:110]}")
+              f"sspill {g('sgpr_spill_count'):>3} lds {g('group_segment_fixed_size'):>6} "
+              f"scratch {g('private_segment_fixed_size'):>5}  {dem[:110]}")
 
 
 if __name__ == "__main__":
