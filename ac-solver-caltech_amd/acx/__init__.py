@@ -3,7 +3,9 @@ path of Avi161/AC-Solver-Caltech), HIP kernels behind the C-ABI in include/acx.h
 
 Public names mirror the reference's ac_solver/__init__.py:1-6 (ACEnv, ACEnvConfig, bfs,
 greedy_search); VecACEnv and acx.ops are the batched device API, bfs_many and greedy_search_many
-are bfs and greedy_search over a batch of presentations in one launch.
+are bfs and greedy_search over a batch of presentations in one launch, beam_search_many and
+beam_search the reference's value-guided beam search (value_search/value_guided_search.py) over a
+batch, scored by the caller's model.
 """
 
 from .envs.ac_env import ACEnv, ACEnvConfig, VecACEnv
@@ -12,7 +14,8 @@ from .search.breadth_first import bfs
 from .search._batch_bfs import bfs_many
 from .search.greedy import greedy_search
 from .search._batch_greedy import greedy_search_many
+from .search._batch_beam import beam_search, beam_search_many
 from . import data  # noqa: F401
 
 __all__ = ["ACEnv", "ACEnvConfig", "VecACEnv", "ACMove", "bfs", "bfs_many", "greedy_search",
-           "greedy_search_many"]
+           "greedy_search_many", "beam_search", "beam_search_many"]

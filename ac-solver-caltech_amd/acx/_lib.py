@@ -124,6 +124,21 @@ for _prefix in ("acx_mbfs", "acx_mgreedy"):
     for _what, _args, _res in _BATCH:
         SIGNATURES[f"{_prefix}_{_what}"] = (_args, _res)
 
+# beam search scored by the caller (ac-solver-caltech_amd/csrc/acx_beam.hip): a step is expand,
+# gather, the scorer, select
+BEAM_NAN, BEAM_MAX_WIDTH = -5, 1024
+SIGNATURES.update({
+    "acx_beam_bytes": ([_I32, _I64, _I32], ctypes.c_int64),
+    "acx_beam_create": ([_I32, _I64, _I64, _I32, _I32], ctypes.c_void_p),
+    "acx_beam_begin": ([_P, _P, _P, _P, _I64, _P], ctypes.c_int),
+    "acx_beam_expand": ([_P, _P, _P], ctypes.c_int),
+    "acx_beam_gather": ([_P, _P, _I64, _P], ctypes.c_int),
+    "acx_beam_select": ([_P, _P, _I64, _P], ctypes.c_int),
+    "acx_beam_finish": ([_P] * 7, ctypes.c_int),
+    "acx_beam_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
+    "acx_beam_destroy": ([_P], None),
+})
+
 _lib = None
 
 

@@ -1,6 +1,7 @@
+from ._batch_beam import beam_search, beam_search_many
 from ._batch_bfs import bfs_many
 from ._batch_greedy import greedy_search_many
 from .breadth_first import bfs
 from .greedy import greedy_search
 
-__all__ = ["bfs", "bfs_many", "greedy_search", "greedy_search_many"]
+__all__ = ["bfs", "bfs_many", "greedy_search", "greedy_search_many", "beam_search", "beam_search_many"]

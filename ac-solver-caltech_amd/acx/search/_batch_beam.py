@@ -1,0 +1,249 @@
+"""beam_search over a batch of presentations, scored by the caller's model (csrc/acx_beam.hip,
+C-ABI acx_beam_* in include/acx.h): one workgroup owns one search -- node store, visited set,
+beam -- and a step of all searches is two launches (expand, select) with the scorer between them,
+called once on every live search's candidates together.  Given equal scores, each result equals
+the reference's beam_search(p_i, ...) (value_search/value_guided_search.py:417-561, with
+solution_cache=None and time_limit=None), paths included: the order-dependent dedup, the budget
+cut in the middle of a parent and the stable top-W selection are exact, and the only floats are
+the scorer's."""
+
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+from . import _batch_bfs
+
+_HANDLES = {}  # (device, L, cyclical) -> (handle, searches, max_nodes_each, max_width)
+MAX_WIDTH = _lib.BEAM_MAX_WIDTH
+NO_PATH = (False, [])
+_TIMING = None  # tools/bench_search_many.py: an object whose mark() is called between a step's phases
+
+
+def release_workspaces() -> None:
+    """Free the cached batch workspaces of the beam search."""
+    if not _HANDLES:
+        return
+    lib = _lib.load()
+    for h in _HANDLES.values():
+        lib.acx_beam_destroy(h[0])
+    _HANDLES.clear()
+
+
+def _handle(lib, dev, L, cyclical, n, max_nodes, max_width):
+    key = (dev.index, L, bool(cyclical))
+    h = _HANDLES.get(key)
+    # (a wider handle selects in a larger LDS class: reused only within its class)
+    if h is not None and h[1] >= n and h[2] >= max_nodes and h[3] >= max_width and _wclass(h[3]) == _wclass(max_width):
+        return h[0]
+    if h is not None:
+        lib.acx_beam_destroy(h[0])
+        del _HANDLES[key]
+    with torch.cuda.device(dev):
+        ptr = lib.acx_beam_create(L, n, max_nodes, max_width, int(bool(cyclical)))
+    if not ptr:
+        raise _lib.ACXError(f"acx_beam_create(L={L}, n_searches={n}, max_nodes_each={max_nodes}, "
+                            f"max_width={max_width}) failed (device memory?)")
+    _HANDLES[key] = (ptr, n, max_nodes, max_width)
+    return ptr
+
+
+def _wclass(w):
+    return 0 if 12 * w <= 1024 else 1 if 12 * w <= 4096 else 2
+
+
+def _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore, scorer_input, feat_mean, feat_std,
+                   on_error):
+    """(states, budgets, widths (N) int32, mean, std as float32 arrays or None) or ValueError; no
+    GPU call."""
+    states, budgets = _batch_bfs._validate(presentations, max_nodes_to_explore, on_error, "beam_search_many")
+    N = len(states)
+    if not callable(scorer):
+        raise ValueError("scorer must be callable")
+    if scorer_input not in ("features", "tokens"):
+        raise ValueError(f"scorer_input must be 'features' or 'tokens', not {scorer_input!r}")
+    if np.ndim(beam_width) == 0:
+        if isinstance(beam_width, (bool, np.bool_)) or not isinstance(beam_width, (int, np.integer)):
+            raise ValueError("beam_width must be an integer or a sequence of integers")
+        w = np.full(N, int(beam_width), np.int64)
+    else:
+        w = np.asarray(beam_width)
+        if w.ndim != 1 or len(w) != N or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError(f"beam_width must be an integer or a sequence of {N} integers")
+        w = w.astype(np.int64)
+    if N and (int(w.min()) < 1 or int(w.max()) > MAX_WIDTH):
+        raise ValueError(f"beam_width must lie in [1, {MAX_WIDTH}]")
+    if (feat_mean is None) != (feat_std is None):
+        raise ValueError("pass both feat_mean and feat_std, or neither")
+    mean = std = None
+    if feat_mean is not None:
+        if scorer_input != "features":
+            raise ValueError("feat_mean / feat_std go with scorer_input='features'")
+        mean, std = (np.ascontiguousarray(torch.as_tensor(x).detach().cpu().numpy(), dtype=np.float32)
+                     for x in (feat_mean, feat_std))
+        if mean.shape != (14,) or std.shape != (14,):
+            raise ValueError("feat_mean and feat_std hold 14 values each")
+    return states, budgets, w.astype(np.int32), mean, std
+
+
+def beam_search_many(presentations, scorer, beam_width=50, max_nodes_to_explore=10000,
+                     cyclically_reduce_after_moves=False, scorer_input="features", feat_mean=None, feat_std=None,
+                     device=None, on_error="raise", return_stats=False, workspace_bytes=None):
+    """beam_search of every row of `presentations` ((N, 2L) array, tensor or list of equal-length
+    rows), all searches stepping together: a list of (True, path) | (False, []), entry i equal to the
+    reference's beam_search(presentations[i], ..., beam_width_i, budget_i) wherever the scorer's
+    values order as the reference's model's do.  Prints nothing.
+
+    scorer: called once per step with one device tensor holding the candidates of every live search,
+      rows in (search, candidate) order: float32 (M, 14) -- compute_features' values, (f - mean) / std
+      when feat_mean and feat_std are given -- or, with scorer_input="tokens", int64 (M, 2L) token
+      ids (letter + 2).  It returns (M,) or (M, 1), taken as float32; lower is better.  Ties keep
+      candidate order and -0.0 ties with +0.0; a NaN raises ValueError.
+    beam_width, max_nodes_to_explore: one value, or one per row (widths 1 .. 1024).
+    on_error: a search in which a move raises in the reference makes the call raise AssertionError
+      naming the rows ("raise"), or puts None at their positions ("return").
+    return_stats: also return a dict of (N) arrays -- status (ACX_BFS_* of include/acx.h;
+      ACX_BFS_EXHAUSTED: a step had no candidate), nodes (the reference's nodes_explored), steps.
+    workspace_bytes: the most device memory the searches' workspace may take (default: half of the
+      free device memory); a larger batch runs as consecutive groups, each with its own steps."""
+    states, budgets, widths, mean, std = _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore,
+                                                        scorer_input, feat_mean, feat_std, on_error)
+    N, L = states.shape[0], states.shape[1] // 2
+    cyc = bool(cyclically_reduce_after_moves)
+    stats = dict(status=np.zeros(N, np.int32), nodes=np.zeros(N, np.int64), steps=np.zeros(N, np.int64))
+    results = [NO_PATH] * N
+    if N:
+        dev = torch.device(device if device is not None else "cuda")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        lib = _lib.load()
+        cap, wcap = int(budgets.max()), int(widths.max())
+        per = int(lib.acx_beam_bytes(L, cap, wcap))
+        if workspace_bytes is None:
+            workspace_bytes = int(_batch_bfs.WORKSPACE_FRACTION * torch.cuda.mem_get_info(dev)[0])
+            have = _HANDLES.get((dev.index, L, cyc))
+            if have is not None:  # a cached workspace is not free memory, but it is ours to use
+                workspace_bytes = max(workspace_bytes, have[1] * int(lib.acx_beam_bytes(L, have[2], have[3])))
+        group = max(1, min(N, int(workspace_bytes) // per))
+        for g0 in range(0, N, group):
+            g1 = min(N, g0 + group)
+            _run_group(lib, dev, L, cyc, states[g0:g1], budgets[g0:g1], widths[g0:g1], group, cap, wcap, scorer,
+                       scorer_input, mean, std, g0, stats, results)
+    nan = np.nonzero(stats["status"] == _lib.BEAM_NAN)[0]
+    if len(nan):
+        raise ValueError(f"beam_search_many: the scorer returned NaN in searches {nan.tolist()}")
+    bad = np.nonzero(stats["status"] < 0)[0]
+    if len(bad):  # validated rows, budgets and widths cannot get here: a full table or a kernel fault
+        raise _lib.ACXError(f"acx_beam: searches {bad.tolist()} ended with status {stats['status'][bad].tolist()}")
+    errs = np.nonzero(stats["status"] == _lib.BFS_MOVE_ERROR)[0]
+    if len(errs):
+        if on_error == "raise":
+            raise AssertionError("beam_search_many: a move produced an invalid presentation (utils.py:264-266) in "
+                                 f"searches {errs.tolist()}")
+        for i in errs:
+            results[int(i)] = None
+    return (results, stats) if return_stats else results
+
+
+def _scores(scorer, x, M):
+    with torch.no_grad():
+        y = scorer(x)
+    if not isinstance(y, torch.Tensor) or y.device != x.device:
+        raise ValueError("the scorer must return a tensor on its input's device")
+    if y.shape not in ((M,), (M, 1)):
+        raise ValueError(f"the scorer must return ({M},) or ({M}, 1) values, not {tuple(y.shape)}")
+    return y.reshape(M).to(torch.float32).contiguous()
+
+
+def _run_group(lib, dev, L, cyc, states, budgets, widths, n_cap, cap, wcap, scorer, scorer_input, mean, std, g0,
+               stats, results):
+    n, kw = len(states), _lib.key_words(L)
+    h = _handle(lib, dev, L, cyc, n_cap, cap, wcap)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        st = torch.from_numpy(states).to(dev)
+        bd = torch.from_numpy(budgets).to(dev)
+        wd = torch.from_numpy(widths).to(dev)
+        mean_d, std_d = (None if x is None else torch.from_numpy(x).to(dev) for x in (mean, std))
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+        _lib.check(lib.acx_beam_begin(h, st.data_ptr(), bd.data_ptr(), wd.data_ptr(), n, stream), "acx_beam_begin")
+        mark = (lambda: None) if _TIMING is None else _TIMING.mark
+        # a step without a verdict adds a node to a search, and a search ends at its budget
+        for _ in range(cap + 2):
+            mark()
+            _lib.check(lib.acx_beam_expand(h, total.data_ptr(), stream), "acx_beam_expand")
+            mark()
+            M = int(total.item())  # the step's one host synchronisation
+            if M == 0:
+                break
+            keys = torch.empty((M, kw), dtype=torch.int64, device=dev)
+            _lib.check(lib.acx_beam_gather(h, keys.data_ptr(), M, stream), "acx_beam_gather")
+            if scorer_input == "features":
+                x = ops.features(keys=keys, L=L, mean=mean_d, std=std_d)
+            else:
+                x = ops.token_ids(keys=keys, L=L)
+            mark()
+            y = _scores(scorer, x, M)
+            mark()
+            _lib.check(lib.acx_beam_select(h, y.data_ptr(), M, stream), "acx_beam_select")
+            mark()
+        else:
+            raise _lib.ACXError("acx_beam: the searches did not end within their budgets")
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        min_len = torch.empty(n, dtype=torch.int32, device=dev)
+        nodes, steps, plen = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+        _lib.check(lib.acx_beam_finish(h, status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(),
+                                       plen.data_ptr(), stream), "acx_beam_finish")
+        offsets = torch.cumsum(plen, 0) - plen
+        plen_h = plen.cpu().numpy()
+        tot = int(plen_h.sum())
+        acts = torch.empty(max(tot, 1), dtype=torch.int32, device=dev)
+        tots = torch.empty(max(tot, 1), dtype=torch.int32, device=dev)
+        if tot:
+            _lib.check(lib.acx_beam_paths(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), tot, stream),
+                       "acx_beam_paths")
+        status_h = status.cpu().numpy()
+        stats["status"][g0:g0 + n] = status_h
+        stats["nodes"][g0:g0 + n] = nodes.cpu().numpy()
+        stats["steps"][g0:g0 + n] = steps.cpu().numpy()
+        acts_h, tots_h = acts.cpu().tolist(), tots.cpu().tolist()
+    off = 0
+    for i in range(n):
+        k = int(plen_h[i])
+        if status_h[i] == _lib.BFS_FOUND:
+            results[g0 + i] = (True, list(zip(acts_h[off:off + k], tots_h[off:off + k])))
+        off += k
+
+
+def beam_search(presentation, model, architecture="mlp", feat_mean=None, feat_std=None, beam_width=50,
+                max_nodes_to_explore=10000, device=None, cyclically_reduce_after_moves=False, verbose=False,
+                solution_cache=None, time_limit=None):
+    """The reference's beam_search (value_search/value_guided_search.py:417-561): (solved, path,
+    stats) with stats = {'nodes_explored', 'steps'}.  The candidates are scored as _score_states_mlp
+    / _score_states_seq score them -- the model on the normalised features ('mlp') or on the token
+    ids (any other architecture), then torch.expm1 -- but on `device` (default: the current GPU),
+    where `model` must live.  With a real float model the result equals the reference's only where
+    the two sides' scores order the same: a GPU's float32 sums are not bit-equal to a CPU's, and a
+    near-tie resolved the other way changes the beam.  Everything else -- expansion order, the
+    visited set, the budget cut, the stable selection -- is exact.
+
+    solution_cache and time_limit are accepted only as None; verbose prints nothing."""
+    if solution_cache is not None or time_limit is not None:
+        raise NotImplementedError("acx.beam_search supports solution_cache=None and time_limit=None only")
+    mlp = architecture == "mlp"
+    if mlp and (feat_mean is None or feat_std is None):
+        raise ValueError("architecture='mlp' needs feat_mean and feat_std")
+
+    def scorer(x):
+        return torch.expm1(model(x).squeeze(-1))
+
+    p = np.asarray(presentation)
+    res, st = beam_search_many(p.reshape(1, -1).astype(np.int32), scorer, beam_width=int(beam_width),
+                               max_nodes_to_explore=int(max_nodes_to_explore),
+                               cyclically_reduce_after_moves=cyclically_reduce_after_moves,
+                               scorer_input="features" if mlp else "tokens", feat_mean=feat_mean if mlp else None,
+                               feat_std=feat_std if mlp else None, device=device, on_error="raise",
+                               return_stats=True)
+    solved, path = res[0]
+    return solved, path, {"nodes_explored": int(st["nodes"][0]), "steps": int(st["steps"][0])}

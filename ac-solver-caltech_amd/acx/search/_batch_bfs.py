@@ -62,10 +62,11 @@ def _release(eng) -> None:
 
 
 def release_workspaces() -> None:
-    """Free the cached batch workspaces (the batched greedy search's too)."""
+    """Free the cached batch workspaces (the batched greedy and beam searches' too)."""
     _release(_BFS)
-    from . import _batch_greedy
+    from . import _batch_beam, _batch_greedy
     _batch_greedy.release_workspaces()
+    _batch_beam.release_workspaces()
 
 
 def _validate(presentations, max_nodes_to_explore, on_error, name="bfs_many"):

@@ -1,0 +1,603 @@
+// acx_beam.hip -- beam search over a batch of presentations, scored by the caller: one workgroup
+// owns one search, and a step of all searches is two launches with the caller's scorer between
+// them.  The searches are independent, so no workgroup ever waits on another.
+//
+// Reference: value_search/value_guided_search.py:417-561 (beam_search) with solution_cache=None
+// and time_limit=None.  The root is node 0 and total_nodes starts at 1; while total_nodes <
+// max_nodes a step makes the beam's children in sequential order s = 12 * (rank in the beam) +
+// action, and for each in that order: a raising move ends the search (ACX_BFS_MOVE_ERROR); a child
+// of total length 2 ends it, found, before the visited test; a child not yet visited becomes the
+// next node and the step's next candidate; if that makes total_nodes >= max_nodes the expansion
+// stops at that child (bfs tests after each parent: acx_bfs_verdict.h is not what happens here).
+// A step without a candidate ends the search (ACX_BFS_EXHAUSTED); otherwise the new beam is the
+// first `width` of a stable sort of the candidates by score.  After a budget cut the candidates are
+// still scored and selected, and the next expand ends the search (ACX_BFS_BUDGET).
+//
+// A search's memory is a private slice of each of the handle's arrays, those of acx_mbfs.hip:
+//   store  (B, kw) uint64   node keys in node_id order (node 0 is the root).  A step's candidates
+//                           are its new nodes, rows cand_base .. cand_base + cand_n, so the gather
+//                           copies them from here and there are no candidate slots to fill;
+//   meta   (B) uint32       parent index << 4 | action;
+//   table  (nb * 8) uint64  the visited set, 8 nb >= 2 (B + 11 + 768);
+//   scratch (768, kw) uint64  only for L > 64: a pass's child keys;
+//   beam   (max_width) uint32  the beam's node indices, best first;
+//   state, res, the five results, the step's candidate count and its offset (140 bytes).
+// Bytes per search (acx_beam_bytes):
+//   8 kw B + 4 B + 64 ceil((B + 779) / 4) + 4 max_width + 140 [+ 6144 kw when L > 64].
+//
+// beam_expand_kernel<NW>: a step is ceil(beam / 64) passes, each a round of acx_mbfs.hip over the
+// next P <= 64 beam entries -- expand, insert, decide, commit, with a barrier between.  The
+// differences: the parents are read through the beam; the cut is the child that holds the
+// (max_nodes - total_nodes)-th survivor in sequential order, found from the per-parent survivor
+// masks, and only survivors up to it are committed; a pass is committed before the next begins, so
+// a later pass meets the earlier ones' children as nodes.  A round code is n + s with n the node
+// count when its pass began: every holder of a pass without a verdict is recoded to its node index
+// (< the next pass's n) at commit, and a pass with a verdict (cut included) is the search's last
+// insert, so no round code is ever read as a node index.
+// beam_select_kernel<CAP>: the candidates' (score key, index) words (acx_beam_key.h) are sorted in
+// LDS by a bitonic network over the next power of two, CAP = 1024, 4096 or 16384 words by the
+// handle's max_width (8, 32, 128 KiB of LDS: the widest class holds one workgroup per CU, which is
+// why a handle of narrow beams does not use it).
+// Every loop is bounded: steps by the budget (a step without a verdict adds a node), passes by
+// max_width / 64, probes by nb, the path walk by the node count.
+//
+// Registers and LDS (hipcc --offload-arch=gfx950 -O3, the kernels' metadata in --save-temps):
+//   beam_expand_kernel<1 / 2 / 3 / 4 / 8>   84 / 90 / 92 / 94 / 126 VGPRs, 18,976 / 25,120 / 31,264 /
+//       37,408 / 6,684 B of LDS: 5, 5, 5, 4, 4 waves per SIMD, as mbfs_kernel (<2> also has 24 B of
+//       private memory per lane; the other widths have none);
+//   beam_select_kernel<1024 / 4096 / 16384>   12 / 12 / 13 VGPRs, 8,200 / 32,776 / 131,080 B of LDS.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "acx.h"
+#include "acx_moves.h"
+
+#include "acx_batch.h"
+#include "acx_beam_key.h"
+#include "acx_bfs_common.h"
+#include "acx_visited.h"
+
+namespace acx {
+namespace beam {
+
+using namespace acx::bfs;
+using batch::Buckets;
+using batch::Res;
+using visited::BUCKET;
+
+constexpr int RP = 64;       // beam entries per pass
+constexpr int RC = 12 * RP;  // children per pass
+
+// a search between two launches
+struct State {
+    int64_t n_nodes, max_nodes, steps, cand_base;
+    int32_t done, beam_n, width, cand_n;
+    uint32_t running;  // min total of the root and the children looked at
+    int32_t pad;
+};
+
+struct Args : batch::Args {
+    uint64_t* scratch;
+    State* state;
+    uint32_t* beam;    // (max_width) per search
+    int32_t* counts;   // (n) the step's candidates per search
+    int64_t* offsets;  // (n + 1) their exclusive prefix sum
+    int32_t max_width;
+    int64_t n;  // searches of the running call
+};
+
+__device__ __forceinline__ void finish(const Args& a, int64_t q, State* S, int32_t status, int32_t act, int64_t node,
+                                       int64_t n_nodes, int64_t steps, uint32_t running, int64_t plen) {
+    batch::write_result(a, q, Res{status, act, node, 2, 0, n_nodes}, steps, running, plen);
+    S->done = 1;
+    S->n_nodes = n_nodes;
+    S->steps = steps;
+    S->cand_n = 0;
+    a.counts[q] = 0;
+}
+
+template <int NW>
+__global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* widths) {
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    const int kw = a.kw;
+    uint64_t* store = a.store + q * a.rows * kw;
+    uint32_t* meta = a.meta + q * a.rows;
+    uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
+    State* S = a.state + q;
+    const batch::Root root = batch::root_setup<TPB, NW>(a, q, store, meta, table);
+    if (tid != 0) return;
+    const int32_t w = widths[q];
+    const bool wide = w < 1 || w > a.max_width;
+    // (a search's results are written where it ends; until then, and for a width out of range:)
+    if (!root.refused) batch::write_result(a, q, Res{ACX_MBFS_OVERFLOW, 0, 0, 0, 0, 0}, 0, 0, 0);
+    *S = State{1, root.max_nodes, 0, 1, root.refused || wide, 1, w, 0, root.total0, 0};
+    a.beam[q * a.max_width] = 0;
+    a.counts[q] = 0;
+}
+
+template <int NW>
+__global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
+    constexpr bool LDS_KEYS = NW <= 4;
+    __shared__ uint64_t kl[LDS_KEYS ? RC * (NW + 1) : 1];
+    __shared__ uint32_t slot[RC];    // table index of the entry a child holds
+    __shared__ uint16_t ctot[RC];    // child total, 0xffff: the move raised (or no such child)
+    __shared__ uint8_t cand[RC];     // the child holds its state's entry after its own probe
+    __shared__ uint8_t lost[RC];     // an earlier child of the pass took that entry
+    __shared__ uint32_t pmask[RP], pexcl[RP];
+    __shared__ uint32_t s_succ, s_err, s_min, s_over;
+    __shared__ uint32_t s_dec[3];    // verdict kind, children looked at, new nodes
+
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
+    const int64_t q = blockIdx.x;
+    const int L = a.L, kw = a.kw;
+    const bool cyc = a.cyc != 0;
+    State* S = a.state + q;
+    if (S->done) return;  // (its count is 0 since it ended)
+    uint64_t* store = a.store + q * a.rows * kw;
+    uint32_t* meta = a.meta + q * a.rows;
+    uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
+    const uint32_t* beam = a.beam + q * a.max_width;
+    uint64_t* ck;
+    if constexpr (LDS_KEYS) ck = kl;
+    else ck = a.scratch + q * (int64_t)RC * kw;
+
+    int64_t n_nodes = S->n_nodes, steps = S->steps;
+    const int64_t max_nodes = S->max_nodes;
+    const int beam_n = S->beam_n;
+    uint32_t running = S->running;
+    if (tid == 0) s_over = 0;
+    __syncthreads();  // the state is read before thread 0 rewrites it
+    if (n_nodes >= max_nodes || beam_n < 1) {  // the reference's loop condition
+        if (tid == 0) finish(a, q, S, beam_n < 1 ? ACX_BFS_EXHAUSTED : ACX_BFS_BUDGET, 0, 0, n_nodes, steps, running, 0);
+        return;
+    }
+    ++steps;
+    const int64_t cand_base = n_nodes;
+    int32_t status = 0, succ_act = 0;
+    int64_t succ_node = 0;
+
+    for (int base = 0; base < beam_n; base += RP) {
+        const int P = beam_n - base < RP ? beam_n - base : RP;
+        const int nch = 12 * P;
+        for (int c = tid; c < RC; c += TPB) {
+            cand[c] = 0;
+            lost[c] = 0;
+            ctot[c] = 0xffffu;
+        }
+        if (tid == 0) s_succ = s_err = NONE;
+        __syncthreads();
+
+        // expand
+        {
+            uint32_t succ = NONE, err = NONE;
+            if (lane < P) {
+                PresRegs<NW> pr;
+                const int64_t pn = beam[base + lane];
+                load_key<NW>(store + (pn < a.rows ? pn : 0) * kw, kw, L, pr);
+                const bool clean = is_clean<NW>(pr.w0, pr.n0, pr.w1, pr.n1, cyc);
+#pragma unroll 1
+                for (int j = 0; j < 3; ++j) {
+                    const int act = wid * 3 + j;
+                    const uint32_t s = (uint32_t)lane * 12u + (uint32_t)act;
+                    PresRegs<NW> c;
+                    const int e = child_of<NW>(pr, clean, act, L, cyc, c);
+                    if (e != ACX_ERR_NONE) {
+                        err = min(err, s);
+                    } else {
+                        const uint32_t tot = (uint32_t)(c.n0 + c.n1);
+                        if (tot == 2) succ = min(succ, s);
+                        ctot[s] = (uint16_t)tot;
+                    }
+                    uint64_t key[NW + 1];
+                    make_key<NW>(L, c, key);
+#pragma unroll
+                    for (int k = 0; k < NW + 1; ++k)
+                        if (k < kw) ck[s * kw + k] = key[k];
+                }
+            }
+            succ = wave_min(succ);
+            err = wave_min(err);
+            if (lane == 0) {
+                if (succ != NONE) atomicMin(&s_succ, succ);
+                if (err != NONE) atomicMin(&s_err, err);
+            }
+        }
+        __syncthreads();
+
+        // insert: the success / raising child ends the search, later children are not looked at
+        const uint32_t end0 = min(s_succ, s_err);
+        const uint64_t NB = (uint64_t)n_nodes;
+        for (int c = tid; c < nch; c += TPB) {
+            if ((uint32_t)c >= end0) continue;
+            const uint64_t code = NB + (uint64_t)c;
+            const Key<NW + 1> key = kload<NW + 1>(ck + c * kw, kw);
+            const visited::Outcome ins = visited::insert(
+                Buckets{table, a.nb}, a.ep, code, khash<NW + 1>(key, kw),
+                [&](uint64_t vc) {
+                    return vc < NB ? keq<NW + 1>(store + vc * kw, key, kw) : keq<NW + 1>(ck + (vc - NB) * kw, key, kw);
+                },
+                [&](uint32_t sl, uint64_t displaced) {  // a later child of the pass that held it learns it lost
+                    slot[c] = sl;
+                    const uint64_t lc = displaced - NB;
+                    if (displaced != visited::NO_CODE && lc < (uint64_t)RC) lost[lc] = 1;
+                });
+            if (ins == visited::FULL) s_over = 1;
+            cand[c] = ins == visited::HELD;
+        }
+        __syncthreads();
+        if (s_over) {  // (uniform) cannot happen at load <= 1/2
+            status = ACX_MBFS_OVERFLOW;
+            break;
+        }
+
+        // decide: the survivors per beam entry, and the child that holds the survivor with which
+        // total_nodes reaches max_nodes (it lies below end0: only those were inserted)
+        if (wid == 0) {
+            uint32_t m = 0;
+            if (lane < P) {
+#pragma unroll
+                for (int act = 0; act < 12; ++act) {
+                    const int c = lane * 12 + act;
+                    if (cand[c] && !lost[c]) m |= 1u << act;
+                }
+            }
+            const uint32_t cnt = __popc(m);
+            const uint32_t x = wave_incl_sum(cnt, lane);
+            const uint32_t total = __shfl(x, WAVE - 1, WAVE);
+            const int64_t need = max_nodes - n_nodes;  // > 0
+            const unsigned long long cutb = __ballot((int64_t)x >= need);
+            uint32_t cutc = NONE;
+            if (cutb) {
+                const int cutp = __builtin_ctzll(cutb);
+                uint32_t act = 0;
+                if (lane == cutp) {  // its (need - survivors before it)-th survivor
+                    uint32_t mm = m;
+                    for (int64_t k = need - (int64_t)(x - cnt); k > 1; --k) mm &= mm - 1;
+                    act = (uint32_t)__builtin_ctz(mm);
+                    m &= (2u << act) - 1u;
+                } else if (lane > cutp) {
+                    m = 0;
+                }
+                cutc = 12u * (uint32_t)cutp + (uint32_t)__shfl((int)act, cutp, WAVE);
+            }
+            pmask[lane] = m;
+            pexcl[lane] = x - cnt;
+            if (lane == 0) {
+                uint32_t kind = 0, looked = (uint32_t)nch;
+                if (cutb) {
+                    kind = ACX_BFS_BUDGET;
+                    looked = cutc + 1;
+                } else if (end0 != NONE) {  // (a move either raises or returns a child: err != succ)
+                    kind = s_err < s_succ ? ACX_BFS_MOVE_ERROR : ACX_BFS_FOUND;
+                    looked = s_err < s_succ ? s_err : s_succ + 1;
+                }
+                s_dec[0] = kind;
+                s_dec[1] = looked;
+                s_dec[2] = cutb ? (uint32_t)need : total;
+                s_min = NONE;
+            }
+        }
+        __syncthreads();
+        const uint32_t kind = s_dec[0], s_end = s_dec[1], newn = s_dec[2];
+
+        // commit: the survivors (up to the cut) become nodes in sequential order
+        if (kind == 0 || kind == ACX_BFS_BUDGET) {
+            for (int c = tid; c < nch; c += TPB) {
+                const int p = c / 12, act = c - 12 * p;
+                const uint32_t m = pmask[p];
+                if (!((m >> act) & 1u)) continue;
+                const int64_t pos = n_nodes + pexcl[p] + __popc(m & ((1u << act) - 1u));
+                if (pos >= a.rows) continue;  // (never: total_nodes <= max_nodes <= rows)
+                for (int k = 0; k < kw; ++k) store[pos * kw + k] = ck[c * kw + k];
+                meta[pos] = (beam[base + p] << 4) | (uint32_t)act;
+                batch::recode_entry(table, slot[c], (uint64_t)pos);
+            }
+        }
+        {
+            uint32_t m = NONE;
+            for (int c = tid; c < nch; c += TPB)
+                if ((uint32_t)c < s_end) m = min(m, (uint32_t)ctot[c]);
+            m = wave_min(m);
+            if (lane == 0 && m != NONE) atomicMin(&s_min, m);
+        }
+        __syncthreads();
+        running = min(running, s_min);
+        n_nodes += newn;
+        if (kind == ACX_BFS_FOUND || kind == ACX_BFS_MOVE_ERROR) {
+            status = (int32_t)kind;
+            if (kind == ACX_BFS_FOUND) {
+                succ_node = beam[base + (s_end - 1) / 12];
+                succ_act = (int32_t)((s_end - 1) % 12);
+            }
+            break;
+        }
+        if (kind == ACX_BFS_BUDGET) break;  // the candidates are still scored and selected
+    }
+
+    if (tid != 0) return;
+    const int64_t cand_n = n_nodes - cand_base;
+    if (status != 0) {
+        // the edges to the success child's parent + (action, 2)
+        const int64_t plen = status == ACX_BFS_FOUND ? batch::path_depth(meta, succ_node, a.rows) + 1 : 0;
+        finish(a, q, S, status, succ_act, succ_node, n_nodes, steps, running, plen);
+    } else if (cand_n == 0) {  // the beam died
+        finish(a, q, S, ACX_BFS_EXHAUSTED, 0, 0, n_nodes, steps, running, 0);
+    } else {
+        S->n_nodes = n_nodes;
+        S->steps = steps;
+        S->cand_base = cand_base;
+        S->cand_n = (int32_t)cand_n;
+        S->running = running;
+        a.counts[q] = (int32_t)cand_n;
+    }
+}
+
+// offsets = exclusive prefix sum of counts (n + 1 entries), *total = their sum: one block
+__global__ __launch_bounds__(1024) void beam_offsets_kernel(Args a, int64_t* total) {
+    __shared__ uint32_t sh[1024 / WAVE];
+    int64_t run = 0;
+    for (int64_t b = 0; b < a.n; b += 1024) {
+        const int64_t i = b + threadIdx.x;
+        const uint32_t v = i < a.n ? (uint32_t)a.counts[i] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan<1024>(v, sh, tot);
+        if (i < a.n) a.offsets[i] = run + ex;
+        run += tot;
+        __syncthreads();  // sh is rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) {
+        a.offsets[a.n] = run;
+        *total = run;
+    }
+}
+
+// the candidates' keys of search q are consecutive rows of its store: one copy per search
+__global__ __launch_bounds__(TPB) void beam_gather_kernel(Args a, uint64_t* keys, int64_t M) {
+    const int64_t q = blockIdx.x;
+    const State* S = a.state + q;
+    const int64_t n = a.counts[q], off = a.offsets[q], base = S->cand_base;
+    if (n <= 0 || off < 0 || off + n > M || base < 0 || base + n > a.rows) return;
+    const uint64_t* src = a.store + (q * a.rows + base) * a.kw;
+    uint64_t* dst = keys + off * a.kw;
+    for (int64_t t = threadIdx.x; t < n * a.kw; t += TPB) dst[t] = src[t];
+}
+
+template <int CAP, int THREADS>
+__global__ __launch_bounds__(THREADS) void beam_select_kernel(Args a, const float* scores, int64_t M) {
+    __shared__ uint64_t sk[CAP];
+    __shared__ uint32_t s_nan;
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    State* S = a.state + q;
+    const int n = a.counts[q];  // 0 for a search that has ended
+    const int64_t off = a.offsets[q];
+    if (n <= 0 || n > CAP || off < 0 || off + n > M) return;
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    if (tid == 0) s_nan = 0;
+    __syncthreads();
+    for (int i = tid; i < n2; i += THREADS) {
+        uint64_t k = ~0ull;  // padding sorts last
+        if (i < n) {
+            const uint32_t bits = __float_as_uint(scores[off + i]);
+            if (score_is_nan(bits)) s_nan = 1;
+            k = sort_key(bits, (uint32_t)i);
+        }
+        sk[i] = k;
+    }
+    __syncthreads();
+    if (s_nan) {  // (uniform) sticky: the search has ended, nothing is selected
+        if (tid == 0) finish(a, q, S, ACX_BEAM_NAN, 0, 0, S->n_nodes, S->steps, S->running, 0);
+        return;
+    }
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < n2 / 2; t += THREADS) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;  // the pair (i, i + j)
+                const uint64_t x = sk[i], y = sk[p];
+                if ((x > y) == ((i & k) == 0)) {
+                    sk[i] = y;
+                    sk[p] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int w = S->width < n ? S->width : n;
+    uint32_t* beam = a.beam + q * a.max_width;
+    const uint32_t cand_base = (uint32_t)S->cand_base;
+    for (int i = tid; i < w && i < a.max_width; i += THREADS) beam[i] = cand_base + (uint32_t)sk[i];
+    if (tid == 0) S->beam_n = w;
+}
+
+__global__ __launch_bounds__(TPB) void beam_finish_kernel(Args a, int32_t* status, int64_t* nodes, int64_t* steps,
+                                                          int32_t* min_length, int64_t* path_len) {
+    const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (q >= a.n) return;
+    status[q] = a.status[q];
+    nodes[q] = a.nodes[q];
+    steps[q] = a.parents[q];
+    min_length[q] = a.min_length[q];
+    path_len[q] = a.path_len[q];
+}
+
+// The reference's path of every found search (value_guided_search.py:87-97,497-498): thread per
+// search, written at offsets[q]: the edges to end_node + (last_act, 2), no root entry.
+__global__ __launch_bounds__(TPB) void beam_path_kernel(Args a, int64_t n, const int64_t* offsets, int32_t* actions,
+                                                        int32_t* totals, int64_t out_cap) {
+    const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (q >= n) return;
+    const Res r = a.res[q];
+    if (r.status != ACX_BFS_FOUND || r.end_node < 0 || r.end_node >= a.rows) return;
+    const uint64_t* store = a.store + q * a.rows * a.kw;
+    const uint32_t* meta = a.meta + q * a.rows;
+    const int64_t d = batch::path_depth(meta, r.end_node, a.rows);
+    const int64_t off = offsets[q];
+    if (off < 0 || off + d + 1 > out_cap) return;
+    int64_t pos = off + d - 1;
+    for (int64_t i = r.end_node; i != 0 && i < a.rows && pos >= off; i = meta[i] >> 4, --pos) {
+        actions[pos] = (int32_t)(meta[i] & 15u);
+        totals[pos] = key_total(store + i * a.kw, a.L);
+    }
+    actions[off + d] = r.last_act;
+    totals[off + d] = r.last_tot;
+}
+
+// what the handle (acx_batch.h) needs of this engine; max_width is set before arrays() is called
+struct Engine {
+    using Args = beam::Args;
+    static int64_t rows_for(int64_t B) { return B; }
+    static uint32_t buckets_for(int64_t B) { return (uint32_t)((2 * (B + 11 + RC) + BUCKET - 1) / BUCKET); }
+    template <class F>
+    static void arrays(Args& a, F f) {
+        const size_t R = (size_t)a.rows, kw = (size_t)a.kw;
+        f(a.store, 8 * kw * R, false);
+        f(a.meta, 4 * R, false);
+        f(a.table, 8 * (size_t)BUCKET * a.nb, true);
+        f(a.res, sizeof(Res), true);
+        f(a.scratch, a.L > 64 ? 8 * kw * RC : 0, false);  // a pass's child keys where they do not stay in LDS
+        f(a.beam, 4 * (size_t)a.max_width, false);
+        f(a.state, sizeof(State), true);  // (zeroed: done = 0 with no candidates before the first begin)
+        f(a.counts, 4, true);
+        f(a.offsets, 16, true);  // n + 1 entries
+        f(a.status, 4, true);
+        f(a.nodes, 8, true);
+        f(a.parents, 8, true);  // steps
+        f(a.min_length, 4, true);
+        f(a.path_len, 8, true);
+    }
+};
+using Handle = batch::Handle<Engine>;
+
+static bool shape(Args& a, int32_t L, int64_t B, int32_t W, int32_t cyclical) {
+    if (W < 1 || W > ACX_BEAM_MAX_WIDTH) return false;
+    a.max_width = W;
+    return batch::shape<Engine>(a, L, B, cyclical);
+}
+
+struct Begin {
+    const Args& a;
+    const int32_t* widths;
+    hipStream_t st;
+    template <int NW>
+    void go() { beam_begin_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a, widths); }
+};
+struct Expand {
+    const Args& a;
+    hipStream_t st;
+    template <int NW>
+    void go() { beam_expand_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a); }
+};
+
+}  // namespace beam
+}  // namespace acx
+
+namespace beam = acx::beam;
+namespace batch = acx::batch;
+using beam::Handle;
+
+extern "C" {
+
+int64_t acx_beam_bytes(int32_t L, int64_t max_nodes_each, int32_t max_width) {
+    beam::Args a{};
+    if (!beam::shape(a, L, max_nodes_each, max_width, 0)) return ACX_E_ARG;
+    size_t sum = 0;
+    beam::Engine::arrays(a, [&](auto*&, size_t b, bool) { sum += b; });
+    return (int64_t)sum;
+}
+
+void* acx_beam_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t max_width, int32_t cyclical) {
+    beam::Args a{};
+    if (n_searches < 1 || n_searches > batch::MAX_SEARCHES || !beam::shape(a, L, max_nodes_each, max_width, cyclical))
+        return nullptr;
+    Handle* S = new (std::nothrow) Handle();
+    if (!S) return nullptr;
+    S->a = a;
+    S->n_cap = n_searches;
+    const size_t n = (size_t)n_searches;
+    bool ok = true;
+    beam::Engine::arrays(S->a, [&](auto*& p, size_t b, bool zero) {
+        ok = ok && (b == 0 || (hipMalloc((void**)&p, n * b) == hipSuccess &&
+                               (!zero || hipMemset(p, 0, n * b) == hipSuccess)));
+    });
+    if (!ok) {
+        (void)hipGetLastError();
+        delete S;
+        return nullptr;
+    }
+    return S;
+}
+
+void acx_beam_destroy(void* h) { delete static_cast<Handle*>(h); }
+
+int acx_beam_begin(void* h, const int32_t* states, const int64_t* budgets, const int32_t* widths, int64_t n,
+                   void* stream) {
+    Handle* S = static_cast<Handle*>(h);
+    if (!S || !states || !budgets || !widths || n < 0 || n > S->n_cap) return ACX_E_ARG;
+    beam::Args& a = S->a;
+    a.n = n;
+    if (n == 0) return ACX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (!acx::visited::next_epoch(S->epoch, a.table, (size_t)S->n_cap * a.nb * acx::visited::BUCKET * 8, st, a.ep))
+        return ACX_E_LAUNCH;
+    a.states = states;
+    a.budgets = budgets;
+    acx::bfs::by_nw(a.L, beam::Begin{a, widths, st});
+    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+}
+
+int acx_beam_expand(void* h, int64_t* total, void* stream) {
+    Handle* S = static_cast<Handle*>(h);
+    if (!S || !total) return ACX_E_ARG;
+    const beam::Args& a = S->a;
+    hipStream_t st = (hipStream_t)stream;
+    if (a.n > 0) acx::bfs::by_nw(a.L, beam::Expand{a, st});
+    beam::beam_offsets_kernel<<<dim3(1), dim3(1024), 0, st>>>(a, total);
+    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+}
+
+int acx_beam_gather(void* h, uint64_t* keys, int64_t M, void* stream) {
+    Handle* S = static_cast<Handle*>(h);
+    if (!S || M < 0 || (M > 0 && !keys)) return ACX_E_ARG;
+    const beam::Args& a = S->a;
+    if (a.n == 0 || M == 0) return ACX_OK;
+    beam::beam_gather_kernel<<<dim3((unsigned)a.n), dim3(acx::bfs::TPB), 0, (hipStream_t)stream>>>(a, keys, M);
+    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+}
+
+int acx_beam_select(void* h, const float* scores, int64_t M, void* stream) {
+    Handle* S = static_cast<Handle*>(h);
+    if (!S || M < 0 || (M > 0 && !scores)) return ACX_E_ARG;
+    const beam::Args& a = S->a;
+    if (a.n == 0 || M == 0) return ACX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int most = 12 * a.max_width;  // candidates of a step
+    if (most <= 1024) beam::beam_select_kernel<1024, 256><<<dim3((unsigned)a.n), dim3(256), 0, st>>>(a, scores, M);
+    else if (most <= 4096) beam::beam_select_kernel<4096, 1024><<<dim3((unsigned)a.n), dim3(1024), 0, st>>>(a, scores, M);
+    else beam::beam_select_kernel<16384, 1024><<<dim3((unsigned)a.n), dim3(1024), 0, st>>>(a, scores, M);
+    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+}
+
+int acx_beam_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, int32_t* min_length, int64_t* path_len,
+                    void* stream) {
+    Handle* S = static_cast<Handle*>(h);
+    if (!S || !status || !nodes || !steps || !min_length || !path_len) return ACX_E_ARG;
+    const beam::Args& a = S->a;
+    if (a.n == 0) return ACX_OK;
+    beam::beam_finish_kernel<<<dim3((unsigned)((a.n + acx::bfs::TPB - 1) / acx::bfs::TPB)), dim3(acx::bfs::TPB), 0,
+                               (hipStream_t)stream>>>(a, status, nodes, steps, min_length, path_len);
+    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+}
+
+int acx_beam_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
+                   void* stream) {
+    Handle* S = static_cast<Handle*>(h);
+    if (!S || !offsets || !actions || !totals || n < 0 || n > S->n_cap || cap < 0) return ACX_E_ARG;
+    if (n == 0) return ACX_OK;
+    beam::beam_path_kernel<<<dim3((unsigned)((n + acx::bfs::TPB - 1) / acx::bfs::TPB)), dim3(acx::bfs::TPB), 0,
+                             (hipStream_t)stream>>>(S->a, n, offsets, actions, totals, cap);
+    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+}
+
+}  // extern "C"

@@ -515,6 +515,64 @@ int acx_mgreedy_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actio
 void acx_mgreedy_destroy(void* h);
 
 /*
+ * Beam search over a batch of presentations, scored by the caller (csrc/acx_beam.hip): one
+ * workgroup owns one search -- node store, visited set, beam -- on a private slice of the handle's
+ * workspace, and a step of all searches is acx_beam_expand, acx_beam_gather, the caller's scorer on
+ * the gathered keys (acx_features / acx_token_ids read them as they are), acx_beam_select.  Given
+ * equal scores every search gives the result of beam_search on its own presentation,
+ * value_search/value_guided_search.py:417-561 with solution_cache=None and time_limit=None.
+ *   acx_beam_bytes   (value_guided_search.py:417-561) workspace bytes per search for budgets up to
+ *                    max_nodes_each = B and widths up to max_width at max_relator_length L,
+ *                    kw = acx_key_words(L):
+ *                      8 kw B + 4 B + 64 ceil((B + 779) / 4) + 4 max_width + 140 [+ 6144 kw when L > 64]
+ *                    (the rows of acx_mbfs_bytes -- a step's candidates are its new nodes, so they
+ *                    are gathered from the node store -- the beam's node indices, the search's
+ *                    state, its verdict record and its five results); ACX_E_ARG for L outside
+ *                    [1, ACX_MAX_L], B outside [1, 2^24] or max_width outside [1, ACX_BEAM_MAX_WIDTH].
+ *   acx_beam_create  (value_guided_search.py:417-561) allocates n_searches times that on the
+ *                    current device; NULL on bad arguments or when the workspace does not fit.
+ *   acx_beam_begin   (value_guided_search.py:450-476) the roots of n <= n_searches searches:
+ *                    `states` DEVICE (n, 2L) int32, `budgets` DEVICE (n) int64 (a budget < 1 behaves
+ *                    as 1: no step is run), `widths` DEVICE (n) int32.  A state outside the packed
+ *                    domain gets ACX_MBFS_DOMAIN, a budget above max_nodes_each or a width outside
+ *                    [1, max_width] ACX_MBFS_OVERFLOW; neither is searched.
+ *   acx_beam_expand  (value_guided_search.py:478-527) one step of every search that has not ended:
+ *                    the beam's children in sequential order 12 * rank + action, the trivial and
+ *                    raising tests, the visited set, the budget cut at the child that meets it; the
+ *                    new nodes are the step's candidates.  `total` DEVICE (1) int64 receives M, the
+ *                    candidates of all searches; M == 0: every search has ended.
+ *   acx_beam_gather  (value_guided_search.py:530-531) `keys` DEVICE (M, kw) uint64: the candidates'
+ *                    packed keys in (search, candidate) order.
+ *   acx_beam_select  (value_guided_search.py:539-541) `scores` DEVICE (M) float32 in that order,
+ *                    lower is better: the new beam of a search is the first `width` of a stable
+ *                    sort of its candidates by score (-0.0 ties with +0.0).  A NaN among a search's
+ *                    scores ends it with ACX_BEAM_NAN; nothing is selected from it.
+ *   acx_beam_finish  (value_guided_search.py:499,560) outputs DEVICE arrays of n: status (an
+ *                    ACX_BFS_* value -- ACX_BFS_EXHAUSTED: a step had no candidate -- or a negative
+ *                    refusal), nodes (total_nodes at the ending event), steps begun, min_length
+ *                    (over the root and the children looked at), path_len.
+ *   acx_beam_paths   (value_guided_search.py:87-97,497-498) for every search with ACX_BFS_FOUND the
+ *                    reference's path [(action, total), ..., (action, 2)] (no root entry) in CSR
+ *                    form at offsets[q], as acx_mbfs_paths writes its paths.
+ *   acx_beam_destroy frees the workspace.
+ * All calls are asynchronous on `stream` and must use the same stream between begin and finish.
+ */
+#define ACX_BEAM_NAN (-5) /* per-search status: the scorer returned NaN for one of its candidates */
+#define ACX_BEAM_MAX_WIDTH 1024
+int64_t acx_beam_bytes(int32_t L, int64_t max_nodes_each, int32_t max_width);
+void* acx_beam_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t max_width, int32_t cyclical);
+int acx_beam_begin(void* h, const int32_t* states, const int64_t* budgets, const int32_t* widths, int64_t n,
+                   void* stream);
+int acx_beam_expand(void* h, int64_t* total, void* stream);
+int acx_beam_gather(void* h, uint64_t* keys, int64_t M, void* stream);
+int acx_beam_select(void* h, const float* scores, int64_t M, void* stream);
+int acx_beam_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, int32_t* min_length, int64_t* path_len,
+                    void* stream);
+int acx_beam_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
+                   void* stream);
+void acx_beam_destroy(void* h);
+
+/*
  * Breadth-first search with the node store and the visited set partitioned over G GPUs by key
  * owner (one process per GPU).  Same results as acx_bfs_run / the
  * reference bfs (breadth_first.py:15-97).  The caller runs the same chunk loop on every rank

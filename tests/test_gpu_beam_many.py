@@ -1,0 +1,352 @@
+"""GPU parity of the batched beam search (acx.beam_search_many / acx.beam_search, csrc/acx_beam.hip:
+one workgroup per search, a step = expand, gather, the caller's scorer, select): with scorers whose
+float32 values are exact, every search gives the reference's beam_search result
+(value_search/value_guided_search.py:417-561) -- against the reference's recorded runs
+(tests/golden/beam_search.json) and against the yardstick tests/beam_yardstick.py (checked on the
+CPU by test_beam_cpu.py).  A call has one scorer, so the fixture's records are grouped by
+(L, flag, scorer)."""
+import functools
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import beam_yardstick as Y
+import weak_hash_common as WH
+from conftest import REPO
+from many_common import AK2, _dataset_rows, _load, _norm, _same, _scrambled
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+AK3 = [1, 1, 1, -2, -2, -2, -2, 1, 2, 1, -2, -1, -2]
+
+
+def _pad(letters, L, n0=7):
+    s = np.zeros(2 * L, np.int32)
+    s[:n0], s[L:L + len(letters) - n0] = letters[:n0], letters[n0:]
+    return s
+
+
+def _many(pres, scorer, W, budgets, cyc=False, **kw):
+    import acx
+    fn = Y.SCORERS[scorer][1] if isinstance(scorer, str) else scorer
+    res, st = acx.beam_search_many(pres, fn, beam_width=W, max_nodes_to_explore=budgets,
+                                   cyclically_reduce_after_moves=cyc, device=DEV, return_stats=True, **kw)
+    assert len(res) == len(pres) and all(len(v) == len(pres) for v in st.values())
+    return [_norm(r) for r in res], st
+
+
+def _check_yardstick(res, st, i, y, tag):
+    assert res[i] == (None if y["raises"] else [y["ok"], y["path"]]), tag
+    assert (st["status"][i], st["nodes"][i], st["steps"][i]) == (y["status"], y["nodes"], y["steps"]), tag
+
+
+def _check_record(res, st, i, c):
+    if c["raises"]:
+        assert res[i] is None and st["status"][i] == Y.MOVE_ERROR, c
+        return
+    assert res[i] == [c["ok"], c["path"]], c
+    assert (st["nodes"][i], st["steps"][i]) == (c["nodes_explored"], c["steps"]), c
+    died = not c["ok"] and c["nodes_explored"] < max(c["budget"], 1)
+    assert st["status"][i] == (Y.FOUND if c["ok"] else Y.EXHAUSTED if died else Y.BUDGET), c
+
+
+@functools.lru_cache(maxsize=None)
+def _groups():
+    groups = {}
+    for c in _load("beam_search.json"):
+        groups.setdefault((c["L"], c["cyclical"], c["scorer"]), []).append(c)
+    return groups
+
+
+def test_every_fixture_record_grouped_into_single_calls(capsys):
+    groups = _groups()
+    assert sum(len(g) for g in groups.values()) >= 120 and {k[0] for k in groups} >= {2, 7, 18, 36, 128}
+    for (L, cyc, scorer), recs in sorted(groups.items()):
+        res, st = _many(np.array([c["presentation"] for c in recs]), scorer, [c["W"] for c in recs],
+                        [c["budget"] for c in recs], cyc, on_error="return")
+        for i, c in enumerate(recs):
+            _check_record(res, st, i, c)
+    assert capsys.readouterr().out == ""  # beam_search_many prints nothing
+
+
+class _Model(torch.nn.Module):
+    def __init__(self, scorer):
+        super().__init__()
+        self.fn = Y.SCORERS[scorer][1]
+
+    def forward(self, f):
+        return self.fn(f)[:, None]
+
+
+@pytest.mark.parametrize("scorer", ["S0", "S1", "S2"])
+def test_fixture_records_through_beam_search(scorer):
+    """the reference's signature, the model's output through expm1 on the GPU: these modules' scores
+    are integers in [0, 80], which expm1 keeps apart and in order in float32 wherever it is computed"""
+    import acx
+    recs = [c for c in _load("beam_search.json") if c["scorer"] == scorer and c["L"] <= 36]
+    assert len(recs) >= 12 and any(c["raises"] for c in recs) == (scorer != "S2")
+    model = _Model(scorer).to(DEV)
+    mean, std = np.zeros(14, np.float32), np.ones(14, np.float32)
+    for c in recs:
+        args = dict(beam_width=c["W"], max_nodes_to_explore=c["budget"], device=DEV,
+                    cyclically_reduce_after_moves=c["cyclical"])
+        if c["raises"]:
+            with pytest.raises(AssertionError, match="invalid presentation"):
+                acx.beam_search(np.array(c["presentation"], np.int8), model, "mlp", mean, std, **args)
+            continue
+        ok, path, stats = acx.beam_search(np.array(c["presentation"], np.int8), model, "mlp", mean, std, **args)
+        assert (ok, [list(x) for x in path], stats) == (c["ok"], c["path"], dict(nodes_explored=c["nodes_explored"],
+                                                                                 steps=c["steps"])), c
+
+
+# ---------------------------------------------------------------------------------------------
+# widths, key-word counts, per-row widths and budgets: against the yardstick
+# ---------------------------------------------------------------------------------------------
+# 6 / 22 / 65 entries: 72 children cross a wave, 264 the workgroup, 780 the pass; 85 | 86 and
+# 341 | 342 are the select kernel's LDS classes (12 W <= 1024, <= 4096, above)
+WIDTH_CALLS = ([1, 5, 6, 21, 22, 64, 65, 85], [86, 341, 7], [342, 1024, 50])
+
+
+@functools.lru_cache(maxsize=None)
+def _width_case(call, scorer):
+    """(presentations, budgets, the yardstick's results) of a call: AK(3) and Miller-Schupp rows"""
+    widths = WIDTH_CALLS[call]
+    rows = _dataset_rows()
+    pres = np.stack([rows[(37 * i) % len(rows)] if i % 2 else _pad(AK3, 18) for i in range(len(widths))])
+    budgets = [min(20000, 40 + 19 * w + 3 * i) for i, w in enumerate(widths)]
+    return pres, budgets, [Y.beam(pres[i], scorer, w, budgets[i]) for i, w in enumerate(widths)]
+
+
+@pytest.mark.parametrize("scorer", ["S0", "S1"])
+@pytest.mark.parametrize("call", range(len(WIDTH_CALLS)))
+def test_widths_and_budgets_per_row_against_yardstick(call, scorer):
+    widths = WIDTH_CALLS[call]
+    pres, budgets, ys = _width_case(call, scorer)
+    res, st = _many(pres, scorer, widths, budgets)
+    for i, w in enumerate(widths):
+        _check_yardstick(res, st, i, ys[i], (scorer, w, budgets[i]))
+
+
+def test_the_width_cases_are_not_vacuous():
+    """by the yardstick's shape report: duplicate children inside one step, a budget cut in the
+    middle of a parent, score ties across the W boundary, and at every width a step that selected
+    from more candidates than the width"""
+    ys = [(w, y) for call in range(len(WIDTH_CALLS)) for scorer in ("S0", "S1")
+          for w, y in zip(WIDTH_CALLS[call], _width_case(call, scorer)[2])]
+    assert any(y["dup_steps"] for _, y in ys) and any(y["cut_mid"] for _, y in ys) and any(y["tie_steps"] for _, y in ys)
+    assert {w for w, y in ys if max(y["cands"], default=0) > w} == {w for c in WIDTH_CALLS for w in c}
+
+
+@pytest.mark.parametrize("L", [16, 17, 32, 33, 48, 49, 64, 65])
+def test_key_word_counts_against_yardstick(L):
+    """one L on each side of every key-word count that by_nw distinguishes"""
+    rng = np.random.default_rng(500 + L)
+    pres = np.stack([_pad(AK3, L), _scrambled(L, rng, 6), _scrambled(L, rng, 9), _pad(AK3[::-1], L, 6)])
+    for scorer, cyc in (("S0", False), ("S1", True)):
+        budgets = [300, 400, 500, 257]
+        res, st = _many(pres, scorer, [22, 5, 65, 3], budgets, cyc)
+        for i in range(len(pres)):
+            _check_yardstick(res, st, i, Y.beam(pres[i], scorer, [22, 5, 65, 3][i], budgets[i], cyc), (L, scorer, i))
+
+
+def test_more_searches_than_resident_workgroups():
+    rows = _dataset_rows()
+    N = 4096
+    res, st = _many(rows[np.arange(N) % len(rows)], "S0", 5, 100)
+    for i in range(len(rows), N):  # identical rows, identical results
+        j = i % len(rows)
+        assert res[i] == res[j] and all(st[k][i] == st[k][j] for k in st), i
+    for j in range(len(rows)):
+        _check_yardstick(res, st, j, Y.beam(rows[j], "S0", 5, 100), j)
+
+
+def _solvable():
+    recs = [c for c in _load("greedy_many.json")["solvable"] if not c["cyclical"]][:40]
+    return np.array([c["presentation"] for c in recs]), [200 + 20 * (i % 7) for i in range(len(recs))]
+
+
+def test_split_call_equals_unsplit_call():
+    from acx import _lib
+    from acx.search import _batch_beam as B
+    pres, budgets = _solvable()
+    whole = _many(pres, "S1", 7, budgets)
+    B.release_workspaces()
+    per = _lib.load().acx_beam_bytes(18, max(budgets), 7)
+    split = _many(pres, "S1", 7, budgets, workspace_bytes=7 * per + per // 2)  # groups of 7: 5 full, one of 5
+    assert B._HANDLES[(0, 18, False)][1] == 7
+    assert _same(split, whole)
+    assert _same(_many(pres, "S1", 7, budgets, workspace_bytes=1), whole)  # never less than one search per call
+    assert any(r[0] for r in whole[0]) and not all(r[0] for r in whole[0])
+
+
+def test_cached_handle_gives_what_a_fresh_one_gives():
+    from acx.search import _batch_beam as B
+    from acx.search import _batch_bfs
+    pres, budgets = _solvable()
+    first, second = (pres[:20], budgets[:20]), (pres[20:][::-1].copy(), budgets[20:][::-1])
+    B.release_workspaces()
+    _many(first[0], "S0", 7, first[1])
+    h = dict(B._HANDLES)
+    assert len(h) == 1
+    again = _many(second[0], "S0", 7, second[1])
+    assert B._HANDLES == h  # the same workspace
+    _batch_bfs.release_workspaces()  # frees the beam workspaces too
+    assert not B._HANDLES
+    fresh = _many(second[0], "S0", 7, second[1])
+    assert _same(again, fresh)
+    for i in range(len(second[0])):
+        _check_yardstick(fresh[0], fresh[1], i, Y.beam(second[0][i], "S0", 7, second[1][i]), i)
+    for _ in range(70):  # past the wrap of the table's 6-bit epoch
+        _many(first[0][:4], "S0", 7, 60)
+    assert _same(_many(second[0], "S0", 7, second[1]), fresh)
+    B.release_workspaces()
+
+
+def test_tokens_scorer():
+    """scorer_input="tokens": int64 (M, 2L) ids, letter + 2; their sum is exact in float32"""
+    seen = []
+
+    def on_tokens(t):
+        seen.append((t.dtype, t.shape[1], int(t.min()), int(t.max())))
+        return t.sum(1).to(torch.float32)
+
+    def on_states(s):
+        return (np.asarray(s, np.int64) + 2).sum(1).astype(np.float32)
+
+    pres = _dataset_rows()[::20]
+    budgets = [150 + 10 * i for i in range(len(pres))]
+    res, st = _many(pres, on_tokens, 6, budgets, scorer_input="tokens")
+    assert seen and all(s[:2] == (torch.int64, 36) and 0 <= s[2] and s[3] <= 4 for s in seen)
+    for i in range(len(pres)):
+        _check_yardstick(res, st, i, Y.beam(pres[i], on_states, 6, budgets[i], on_states=True), i)
+    assert st["steps"].min() >= 3  # the beams were selected by these scores, more than once
+
+
+def test_nan_scorer_raises_and_leaves_the_handle_usable():
+    import acx
+    from acx.search import _batch_beam as B
+    pres = np.array([[1, 0, 0, 0, 0, 0, 0, 2, 0, 0, 0, 0, 0, 0], AK2, AK2])  # row 0 is found before any scoring
+    B.release_workspaces()
+    want = _many(pres, "S1", 50, 3000)
+    h = dict(B._HANDLES)
+    calls = []
+
+    def nan(f):
+        calls.append(len(f))
+        return f[:, 0] * float("nan")
+
+    with pytest.raises(ValueError, match=r"NaN in searches \[1, 2\]"):
+        acx.beam_search_many(pres, nan, beam_width=50, max_nodes_to_explore=3000, device=DEV)
+    assert calls and B._HANDLES == h
+    assert _same(_many(pres, "S1", 50, 3000), want) and want[0][0][0] and want[0][1][0]
+
+
+# ---------------------------------------------------------------------------------------------
+# the C-ABI: refusal statuses, and the calls of a step one by one
+# ---------------------------------------------------------------------------------------------
+def _drive(lib, h, states, budgets, widths, L, scorer="S0"):
+    from acx import _lib, ops
+    n, kw = len(states), _lib.key_words(L)
+    stream = torch.cuda.current_stream(DEV).cuda_stream
+    fn = Y.SCORERS[scorer][1]
+    with torch.cuda.device(DEV):
+        st = torch.from_numpy(np.ascontiguousarray(states, np.int32)).to(DEV)
+        bd = torch.tensor(budgets, dtype=torch.int64, device=DEV)
+        wd = torch.tensor(widths, dtype=torch.int32, device=DEV)
+        total = torch.zeros(1, dtype=torch.int64, device=DEV)
+        assert lib.acx_beam_begin(h, st.data_ptr(), bd.data_ptr(), wd.data_ptr(), n, stream) == 0
+        for _ in range(max(budgets) + 2):
+            assert lib.acx_beam_expand(h, total.data_ptr(), stream) == 0
+            M = int(total.item())
+            if M == 0:
+                break
+            keys = torch.empty((M, kw), dtype=torch.int64, device=DEV)
+            assert lib.acx_beam_gather(h, keys.data_ptr(), M, stream) == 0
+            y = fn(ops.features(keys=keys, L=L)).to(torch.float32).contiguous()
+            assert lib.acx_beam_select(h, y.data_ptr(), M, stream) == 0
+        else:
+            raise AssertionError("the searches did not end")
+        status, min_len = (torch.full((n,), -77, dtype=torch.int32, device=DEV) for _ in range(2))
+        nodes, steps, plen = (torch.full((n,), -77, dtype=torch.int64, device=DEV) for _ in range(3))
+        assert lib.acx_beam_finish(h, status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(),
+                                   plen.data_ptr(), stream) == 0
+        out = dict(status=status.cpu().numpy(), nodes=nodes.cpu().numpy(), steps=steps.cpu().numpy(),
+                   min_length=min_len.cpu().numpy(), path_len=plen.cpu().numpy())
+        stride = int(out["path_len"].max()) + 3
+        offsets = torch.arange(n, dtype=torch.int64, device=DEV) * stride
+        acts, tots = (torch.full((n * stride,), -77, dtype=torch.int32, device=DEV) for _ in range(2))
+        assert lib.acx_beam_paths(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), n * stride, stream) == 0
+        out["acts"], out["tots"] = acts.cpu().numpy().reshape(n, stride), tots.cpu().numpy().reshape(n, stride)
+    return out
+
+
+def _check_search(out, i, y):
+    assert (out["status"][i], out["nodes"][i], out["steps"][i]) == (y["status"], y["nodes"], y["steps"]), i
+    k = len(y["path"])
+    assert out["path_len"][i] == k, i
+    assert [list(e) for e in zip(out["acts"][i][:k].tolist(), out["tots"][i][:k].tolist())] == y["path"], i
+    assert (out["acts"][i][k:] == -77).all() and (out["tots"][i][k:] == -77).all(), i
+
+
+@pytest.mark.parametrize("L", [13, 36])
+def test_refused_searches_through_the_c_abi(L):
+    """ACX_MBFS_DOMAIN for a row outside the packed domain, ACX_MBFS_OVERFLOW for a budget above the
+    handle's and for a width outside [1, max_width]: all-zero outputs, no path, the other searches
+    undisturbed, nothing left behind for the handle's next run"""
+    from acx import _lib
+    from test_gpu_batch_refusals import _rows
+    lib = _lib.load()
+    CAP, WCAP = 64, 8
+    batch, valid = _rows(L)  # rows 1 .. 4 outside the domain, rows 0, 5, 6 the same valid row
+    batch = np.concatenate([batch, valid[:3]])
+    budgets = [40, 40, 40, 40, 40, 65, 40, 40, 40, 40]
+    widths = [3, 3, 3, 3, 3, 3, 3, 0, 9, 8]
+    with torch.cuda.device(DEV):
+        h = lib.acx_beam_create(L, 10, CAP, WCAP, 0)
+    assert h
+    try:
+        out = _drive(lib, h, batch, budgets, widths, L)
+        want = [0, _lib.MBFS_DOMAIN, _lib.MBFS_DOMAIN, _lib.MBFS_DOMAIN, _lib.MBFS_DOMAIN, _lib.MBFS_OVERFLOW, 0,
+                _lib.MBFS_OVERFLOW, _lib.MBFS_OVERFLOW, 0]
+        for i, w in enumerate(want):
+            if w < 0:
+                assert out["status"][i] == w and (out["acts"][i] == -77).all(), i
+                assert (out["nodes"][i], out["steps"][i], out["min_length"][i], out["path_len"][i]) == (0, 0, 0, 0), i
+            else:
+                _check_search(out, i, Y.beam(batch[i], "S0", widths[i], budgets[i]))
+        # the epoch: the same handle, seven valid rows -- a refused search left nothing behind
+        out = _drive(lib, h, valid, [50] * 7, [8, 1, 2, 3, 4, 5, 6], L)
+        ys = [Y.beam(valid[i], "S0", [8, 1, 2, 3, 4, 5, 6][i], 50) for i in range(7)]
+        for i, y in enumerate(ys):
+            _check_search(out, i, y)
+        assert any(y["ok"] and len(y["path"]) >= 2 for y in ys)  # paths are written and walked
+    finally:
+        lib.acx_beam_destroy(h)
+
+
+def test_weak_hash_run_in_a_process_of_its_own(tmp_path):
+    """AK(3), S0, W = 50 through libacx_weakhash.so (8 hash classes: every probe meets entries of
+    other states with its fingerprint): the results are those of the shipped library"""
+    job = dict(pres=[_pad(AK3, 18).tolist()], scorer="S0", W=50, budget=3000, cyc=False)
+    with open(tmp_path / "in.json", "w") as f:
+        json.dump(job, f)
+    env = dict(os.environ, ACX_LIB=WH.variant())
+    try:
+        r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "beam_weak_hash_child.py"), str(tmp_path)],
+                           env=env, capture_output=True, text=True, timeout=300)
+    except subprocess.TimeoutExpired as e:
+        raise WH.ChildDied(f"timeout: {str(e.stderr)[-2000:]}") from None
+    if r.returncode < 0 or r.returncode in WH.FATAL:
+        raise WH.ChildDied(f"exit code {r.returncode}: {r.stderr[-2000:]}")
+    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    WH.check_classes(got["nodes"][0], got["classes"][0], "beam AK3")
+    res, st = _many(np.array(job["pres"], np.int32), "S0", 50, 3000)
+    assert got["res"] == res and got["st"] == {k: v.tolist() for k, v in st.items()}
+    assert st["nodes"][0] == got["nodes"][0] >= 512

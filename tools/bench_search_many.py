@@ -2,7 +2,7 @@
 budget 10^4, not cyclical -- what the reference's trivialize_miller_schupp_through_search (and, for
 greedy, scripts/parallel_search.py) does, one search per presentation.
 
-    python tools/bench_search_many.py --engine bfs|greedy [--budget N] [--rows N] [--out PATH]
+    python tools/bench_search_many.py --engine bfs|greedy|beam [--budget N] [--rows N] [--out PATH]
 
 Once as a loop of acx.bfs / acx.greedy_search with engine="device" (one search per call,
 csrc/acx_bfs.hip / csrc/acx_greedy.hip) and once as one acx.bfs_many / acx.greedy_search_many call
@@ -12,7 +12,17 @@ fails otherwise).  Writes both wall times, their ratio, the launches and the wor
 JSON (default profiles/bfs_many/bench_bfs_many.json or profiles/greedy_many/bench_greedy_many.json)
 and prints the same line.  For greedy it also counts how many of the shipped greedy-solved set
 (acx/data/greedy_solved_presentations.npy) are among the solved ones at this budget and
-max_relator_length."""
+max_relator_length.
+
+--engine beam: the same rows through one acx.beam_search_many call (csrc/acx_beam.hip), W = 50,
+scorer S0 = the total length (the first feature), timed the same way, with the split of a step into
+expand, gather + features (the host's read of the candidate count falls in it), scorer and select
+from HIP events of a further run.  Beside it the same search written with the parent commit's public
+API -- ops.expand12 once per step over every live beam, the children copied to the host, the
+visited sets, the budget cut and the stable selection in Python -- on every fifth row (238), run
+once after a warm-up on 8 rows; its wall time is scaled by rows / 238 to set it beside the batch
+call, and the JSON says so.  The results of those 238 rows must be equal.  Writes
+profiles/beam_many/bench_beam_many.json."""
 import argparse
 import contextlib
 import io
@@ -41,12 +51,13 @@ ENGINES = {
 }
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--engine", choices=sorted(ENGINES), required=True)
+ap.add_argument("--engine", choices=sorted(ENGINES) + ["beam"], required=True)
+ap.add_argument("--width", type=int, default=50, help="beam width (--engine beam)")
 ap.add_argument("--budget", type=int, default=10 ** 4)
 ap.add_argument("--rows", type=int, default=0, help="only the first N presentations (0: all)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-E = ENGINES[args.engine]
+E = ENGINES.get(args.engine)
 if args.out is None:
     args.out = os.path.join(REPO, "profiles", f"{args.engine}_many", f"bench_{args.engine}_many.json")
 
@@ -87,6 +98,143 @@ def norm(res):
     return [(bool(ok), None if path is None else [tuple(int(v) for v in e) for e in path]) for ok, path in res]
 
 
+def s0(f):
+    return f[:, 0]
+
+
+class Marks:
+    """HIP events at the marks of _batch_beam._run_group: per step before / after expand, after
+    gather + features, after the scorer, after select (the last step ends after its expand)"""
+    NAMES = ("expand", "gather_features", "scorer", "select")
+
+    def __init__(self):
+        self.ev = []
+
+    def mark(self):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        self.ev.append(e)
+
+    def split(self):
+        torch.cuda.synchronize()
+        ms, steps, i = dict.fromkeys(self.NAMES, 0.0), 0, 0
+        while i + 1 < len(self.ev):
+            k = min(5, len(self.ev) - i)
+            for j in range(k - 1):
+                ms[self.NAMES[j]] += self.ev[i + j].elapsed_time(self.ev[i + j + 1])
+            steps += 1
+            i += k
+        return {"steps": steps, **{f"{n}_ms": v for n, v in ms.items()}}
+
+
+def host_beam(rows, W, budget):
+    """beam_search of every row with ops.expand12 as the only device call: [(ok, path)], nodes"""
+    n = len(rows)
+    beams = [[(r, 0)] for r in rows]
+    visited = [{r.tobytes()} for r in rows]
+    parent = [{0: None} for _ in rows]
+    nodes, live, res = [1] * n, list(range(n)), [(False, [])] * n
+    while live:
+        live = [q for q in live if beams[q] and nodes[q] < budget]
+        if not live:
+            break
+        par = torch.from_numpy(np.stack([b[0] for q in live for b in beams[q]])).to(dev)
+        out = acx.ops.expand12(par, cyclical=False)
+        ch, lens, err = (out[k].cpu().numpy() for k in ("children", "lengths", "err"))
+        tot = lens.sum(2)
+        base, nxt = 0, []
+        for q in live:
+            new, done = [], False
+            for r, (_, pid) in enumerate(beams[q]):
+                for a in range(12):
+                    assert not err[base + r, a]
+                    t = int(tot[base + r, a])
+                    if t == 2:
+                        path, v = [(a, 2)], pid
+                        while parent[q][v] is not None:
+                            path.append(parent[q][v][:2])
+                            v = parent[q][v][2]
+                        res[q], done = (True, path[::-1]), True
+                        break
+                    key = ch[base + r, a].tobytes()
+                    if key not in visited[q]:
+                        visited[q].add(key)
+                        parent[q][nodes[q]] = (a, t, pid)
+                        new.append((ch[base + r, a], nodes[q], t))
+                        nodes[q] += 1
+                        if nodes[q] >= budget:
+                            done = None
+                            break
+                if done is not False:
+                    break
+            base += len(beams[q])
+            if done:
+                continue
+            new.sort(key=lambda c: float(c[2]))  # stable
+            beams[q] = [(c[0], c[1]) for c in new[:W]]
+            if new:
+                nxt.append(q)
+        live = nxt
+    return res, nodes
+
+
+def bench_beam():
+    from acx.search import _batch_beam
+    W = args.width
+
+    def many(r=rows):
+        return acx.beam_search_many(r, s0, beam_width=W, max_nodes_to_explore=args.budget, device=dev,
+                                    return_stats=True)
+
+    (batch_res, stats), batch_walls = timed(many, "batch")
+    marks = Marks()
+    _batch_beam._TIMING = marks
+    try:
+        many()
+    finally:
+        _batch_beam._TIMING = None
+    sub = rows[::5]
+    host_beam(sub[:8], W, args.budget)  # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    host_res, host_nodes = host_beam(sub, W, args.budget)
+    host_wall = time.perf_counter() - t0
+    print(f"host: {host_wall * 1e3:.2f} ms for {len(sub)} rows", file=sys.stderr, flush=True)
+    assert norm(host_res) == norm(batch_res[::5]), "beam_search_many and the host-side beam search disagree"
+    assert np.array_equal(stats["nodes"][::5], np.array(host_nodes))
+    h = _batch_beam._HANDLES[(0, L, False)]
+    return {
+        "workload": f"beam_search of {N} Miller-Schupp presentations, L = {L}, W = {W}, budget {args.budget}, "
+                    "scorer S0 (total length), not cyclical",
+        "device": torch.cuda.get_device_name(dev),
+        "searches": N, "solved": int(sum(bool(r[0]) for r in batch_res)),
+        "left_on_budget": int((stats["status"] == _lib.BFS_BUDGET).sum()),
+        "beam_died": int((stats["status"] == _lib.BFS_EXHAUSTED).sum()),
+        "nodes_total": int(stats["nodes"].sum()), "steps_max": int(stats["steps"].max()),
+        "batch_wall_ms": min(batch_walls) * 1e3, "batch_walls_ms": [w * 1e3 for w in batch_walls],
+        "batch_step_split_hip_events": marks.split(),
+        "host_rows": len(sub), "host_wall_ms": host_wall * 1e3, "host_runs": 1,
+        "host_wall_scaled_to_all_rows_ms": host_wall * 1e3 * N / len(sub),
+        "host_scaled_note": f"the host-side search ran on every fifth row ({len(sub)}); its wall time is scaled by "
+                            f"{N}/{len(sub)} to stand beside the batch call",
+        "host_scaled_over_batch": host_wall * N / len(sub) / min(batch_walls),
+        "batch_workspace_bytes": int(h[1] * _lib.load().acx_beam_bytes(L, h[2], h[3])),
+        "results_equal": True,
+    }
+
+
+def write(out):
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if args.engine == "beam":
+    write(bench_beam())
+    sys.exit(0)
+
 (loop_res, loop_nodes), loop_walls = timed(loop, "loop")
 (batch_res, stats), batch_walls = timed(batch, "batch")
 assert norm(batch_res) == norm(loop_res), f"{E['many'].__name__} and the loop of acx.{E['one'].__name__} disagree"
@@ -117,8 +265,4 @@ out.update({
     "batch_launches": -(-N // h[1]), "batch_workspace_bytes": int(h[1] * getattr(_lib.load(), E["bytes"])(L, h[2])),
     "results_equal": True,
 })
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(out, f, indent=1)
-    f.write("\n")
-print(json.dumps(out))
+write(out)
