@@ -21,36 +21,18 @@ NO_PATH = (False, [])
 _TIMING = None  # tools/bench_search_many.py: an object whose mark() is called between a step's phases
 
 
-def release_workspaces() -> None:
-    """Free the cached batch workspaces of the beam search."""
-    if not _HANDLES:
-        return
-    lib = _lib.load()
-    for h in _HANDLES.values():
-        lib.acx_beam_destroy(h[0])
-    _HANDLES.clear()
-
-
-def _handle(lib, dev, L, cyclical, n, max_nodes, max_width):
-    key = (dev.index, L, bool(cyclical))
-    h = _HANDLES.get(key)
-    # (a wider handle selects in a larger LDS class: reused only within its class)
-    if h is not None and h[1] >= n and h[2] >= max_nodes and h[3] >= max_width and _wclass(h[3]) == _wclass(max_width):
-        return h[0]
-    if h is not None:
-        lib.acx_beam_destroy(h[0])
-        del _HANDLES[key]
-    with torch.cuda.device(dev):
-        ptr = lib.acx_beam_create(L, n, max_nodes, max_width, int(bool(cyclical)))
-    if not ptr:
-        raise _lib.ACXError(f"acx_beam_create(L={L}, n_searches={n}, max_nodes_each={max_nodes}, "
-                            f"max_width={max_width}) failed (device memory?)")
-    _HANDLES[key] = (ptr, n, max_nodes, max_width)
-    return ptr
-
-
 def _wclass(w):
     return 0 if 12 * w <= 1024 else 1 if 12 * w <= 4096 else 2
+
+
+# (a wider handle selects in a larger LDS class: reused only within its class)
+_BEAM = _batch_bfs._Engine("beam_search_many", "acx_beam", _HANDLES, (_lib.BFS_FOUND,), NO_PATH, extra=("max_width",),
+                           reuse=lambda have, want: _wclass(have[0]) == _wclass(want[0]))
+
+
+def release_workspaces() -> None:
+    """Free the cached batch workspaces of the beam search."""
+    _batch_bfs._release(_BEAM)
 
 
 def _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore, scorer_input, feat_mean, feat_std,
@@ -110,22 +92,12 @@ def beam_search_many(presentations, scorer, beam_width=50, max_nodes_to_explore=
     states, budgets, widths, mean, std = _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore,
                                                         scorer_input, feat_mean, feat_std, on_error)
     N, L = states.shape[0], states.shape[1] // 2
-    cyc = bool(cyclically_reduce_after_moves)
     stats = dict(status=np.zeros(N, np.int32), nodes=np.zeros(N, np.int64), steps=np.zeros(N, np.int64))
     results = [NO_PATH] * N
     if N:
-        dev = torch.device(device if device is not None else "cuda")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        lib = _lib.load()
+        dev, lib, cyc = _batch_bfs._device(device), _lib.load(), bool(cyclically_reduce_after_moves)
         cap, wcap = int(budgets.max()), int(widths.max())
-        per = int(lib.acx_beam_bytes(L, cap, wcap))
-        if workspace_bytes is None:
-            workspace_bytes = int(_batch_bfs.WORKSPACE_FRACTION * torch.cuda.mem_get_info(dev)[0])
-            have = _HANDLES.get((dev.index, L, cyc))
-            if have is not None:  # a cached workspace is not free memory, but it is ours to use
-                workspace_bytes = max(workspace_bytes, have[1] * int(lib.acx_beam_bytes(L, have[2], have[3])))
-        group = max(1, min(N, int(workspace_bytes) // per))
+        group = _batch_bfs._group_size(_BEAM, lib, dev, L, cyc, N, cap, workspace_bytes, (wcap,))
         for g0 in range(0, N, group):
             g1 = min(N, g0 + group)
             _run_group(lib, dev, L, cyc, states[g0:g1], budgets[g0:g1], widths[g0:g1], group, cap, wcap, scorer,
@@ -133,17 +105,8 @@ def beam_search_many(presentations, scorer, beam_width=50, max_nodes_to_explore=
     nan = np.nonzero(stats["status"] == _lib.BEAM_NAN)[0]
     if len(nan):
         raise ValueError(f"beam_search_many: the scorer returned NaN in searches {nan.tolist()}")
-    bad = np.nonzero(stats["status"] < 0)[0]
-    if len(bad):  # validated rows, budgets and widths cannot get here: a full table or a kernel fault
-        raise _lib.ACXError(f"acx_beam: searches {bad.tolist()} ended with status {stats['status'][bad].tolist()}")
-    errs = np.nonzero(stats["status"] == _lib.BFS_MOVE_ERROR)[0]
-    if len(errs):
-        if on_error == "raise":
-            raise AssertionError("beam_search_many: a move produced an invalid presentation (utils.py:264-266) in "
-                                 f"searches {errs.tolist()}")
-        for i in errs:
-            results[int(i)] = None
-    return (results, stats) if return_stats else results
+    _batch_bfs._check_status("acx_beam", stats["status"])
+    return _batch_bfs._finish(_BEAM, results, stats, on_error, return_stats)
 
 
 def _scores(scorer, x, M):
@@ -159,7 +122,7 @@ def _scores(scorer, x, M):
 def _run_group(lib, dev, L, cyc, states, budgets, widths, n_cap, cap, wcap, scorer, scorer_input, mean, std, g0,
                stats, results):
     n, kw = len(states), _lib.key_words(L)
-    h = _handle(lib, dev, L, cyc, n_cap, cap, wcap)
+    h = _batch_bfs._handle(_BEAM, lib, dev, L, cyc, n_cap, cap, (wcap,))
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
         st = torch.from_numpy(states).to(dev)
@@ -195,25 +158,9 @@ def _run_group(lib, dev, L, cyc, states, budgets, widths, n_cap, cap, wcap, scor
         nodes, steps, plen = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
         _lib.check(lib.acx_beam_finish(h, status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(),
                                        plen.data_ptr(), stream), "acx_beam_finish")
-        offsets = torch.cumsum(plen, 0) - plen
-        plen_h = plen.cpu().numpy()
-        tot = int(plen_h.sum())
-        acts = torch.empty(max(tot, 1), dtype=torch.int32, device=dev)
-        tots = torch.empty(max(tot, 1), dtype=torch.int32, device=dev)
-        if tot:
-            _lib.check(lib.acx_beam_paths(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), tot, stream),
-                       "acx_beam_paths")
-        status_h = status.cpu().numpy()
-        stats["status"][g0:g0 + n] = status_h
+        stats["status"][g0:g0 + n] = _batch_bfs._read_results(_BEAM, lib, h, dev, stream, g0, status, plen, results)
         stats["nodes"][g0:g0 + n] = nodes.cpu().numpy()
         stats["steps"][g0:g0 + n] = steps.cpu().numpy()
-        acts_h, tots_h = acts.cpu().tolist(), tots.cpu().tolist()
-    off = 0
-    for i in range(n):
-        k = int(plen_h[i])
-        if status_h[i] == _lib.BFS_FOUND:
-            results[g0 + i] = (True, list(zip(acts_h[off:off + k], tots_h[off:off + k])))
-        off += k
 
 
 def beam_search(presentation, model, architecture="mlp", feat_mean=None, feat_std=None, beam_width=50,

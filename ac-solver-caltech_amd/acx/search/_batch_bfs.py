@@ -20,13 +20,17 @@ WORKSPACE_FRACTION = 0.5
 
 
 class _Engine:
-    """One batched search of the library: the C functions `prefix`_bytes / _create / _run / _paths /
-    _destroy, its cached handles, and which searches return a path.  _batch_greedy.py runs the
-    batched greedy search through the same code."""
+    """One batched search of the library: the C functions `prefix`_bytes / _create / _paths /
+    _destroy (and _run, or the beam search's step calls), its cached handles, and which searches
+    return a path.  `extra` names the shape arguments its _bytes and _create take after
+    max_nodes_each (beam: max_width); a cached handle whose extras are at least the wanted ones is
+    reused if `reuse(cached extras, wanted extras)` also agrees.  _batch_greedy.py and
+    _batch_beam.py run their searches through the same code."""
 
-    def __init__(self, name, prefix, handles, path_statuses, no_path):
+    def __init__(self, name, prefix, handles, path_statuses, no_path, extra=(), reuse=None):
         self.name, self.prefix, self.handles = name, prefix, handles
         self.path_statuses, self.no_path = path_statuses, no_path
+        self.extra, self.reuse = extra, reuse
 
     def fn(self, lib, what):
         return getattr(lib, f"{self.prefix}_{what}")
@@ -35,29 +39,48 @@ class _Engine:
 _BFS = _Engine("bfs_many", "acx_mbfs", _HANDLES, (_lib.BFS_FOUND,), (False, None))
 
 
-def _handle(eng, lib, dev: torch.device, L: int, cyclical: bool, n: int, max_nodes: int):
+def _device(device) -> torch.device:
+    dev = torch.device(device if device is not None else "cuda")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _handle(eng, lib, dev: torch.device, L: int, cyclical: bool, n: int, max_nodes: int, extra=()):
     key = (dev.index, L, bool(cyclical))
     h = eng.handles.get(key)
-    if h is not None and h[1] >= n and h[2] >= max_nodes:
+    if (h is not None and h[1] >= n and h[2] >= max_nodes and all(a >= b for a, b in zip(h[3:], extra))
+            and (eng.reuse is None or eng.reuse(h[3:], extra))):
         return h[0]
     if h is not None:
         eng.fn(lib, "destroy")(h[0])
         del eng.handles[key]
     with torch.cuda.device(dev):
-        ptr = eng.fn(lib, "create")(L, n, max_nodes, int(bool(cyclical)))
+        ptr = eng.fn(lib, "create")(L, n, max_nodes, *extra, int(bool(cyclical)))
     if not ptr:
-        raise _lib.ACXError(f"{eng.prefix}_create(L={L}, n_searches={n}, max_nodes_each={max_nodes}) failed "
+        shape = "".join(f", {k}={v}" for k, v in zip(eng.extra, extra))
+        raise _lib.ACXError(f"{eng.prefix}_create(L={L}, n_searches={n}, max_nodes_each={max_nodes}{shape}) failed "
                             "(device memory?)")
-    eng.handles[key] = (ptr, n, max_nodes)
+    eng.handles[key] = (ptr, n, max_nodes, *extra)
     return ptr
+
+
+def _group_size(eng, lib, dev, L, cyclical, N, max_nodes, workspace_bytes, extra=()):
+    """how many of N searches run at once: what fits workspace_bytes (None: WORKSPACE_FRACTION of
+    the free device memory), at least one"""
+    per = int(eng.fn(lib, "bytes")(L, max_nodes, *extra))
+    if workspace_bytes is None:
+        workspace_bytes = int(WORKSPACE_FRACTION * torch.cuda.mem_get_info(dev)[0])
+        have = eng.handles.get((dev.index, L, bool(cyclical)))
+        if have is not None:  # a cached workspace is not free memory, but it is ours to use
+            workspace_bytes = max(workspace_bytes, have[1] * int(eng.fn(lib, "bytes")(L, *have[2:])))
+    return max(1, min(N, int(workspace_bytes) // per))
 
 
 def _release(eng) -> None:
     if not eng.handles:
         return
     lib = _lib.load()
-    for ptr, _, _ in eng.handles.values():
-        eng.fn(lib, "destroy")(ptr)
+    for h in eng.handles.values():
+        eng.fn(lib, "destroy")(h[0])
     eng.handles.clear()
 
 
@@ -138,22 +161,17 @@ def _search_many(eng, presentations, max_nodes_to_explore, cyclically_reduce_aft
                  min_length=np.zeros(N, np.int32))
     results = [eng.no_path] * N
     if N:
-        dev = torch.device(device if device is not None else "cuda")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        lib = _lib.load()
+        dev, lib, cyc = _device(device), _lib.load(), bool(cyclically_reduce_after_moves)
         cap = int(budgets.max())
-        per = int(eng.fn(lib, "bytes")(L, cap))
-        if workspace_bytes is None:
-            workspace_bytes = int(WORKSPACE_FRACTION * torch.cuda.mem_get_info(dev)[0])
-            have = eng.handles.get((dev.index, L, bool(cyclically_reduce_after_moves)))
-            if have is not None:  # a cached workspace is not free memory, but it is ours to use
-                workspace_bytes = max(workspace_bytes, have[1] * int(eng.fn(lib, "bytes")(L, have[2])))
-        group = max(1, min(N, int(workspace_bytes) // per))
+        group = _group_size(eng, lib, dev, L, cyc, N, cap, workspace_bytes)
         for g0 in range(0, N, group):
             g1 = min(N, g0 + group)
-            _run_group(eng, lib, dev, L, bool(cyclically_reduce_after_moves), states[g0:g1], budgets[g0:g1], group,
-                       cap, g0, stats, results)
+            _run_group(eng, lib, dev, L, cyc, states[g0:g1], budgets[g0:g1], group, cap, g0, stats, results)
+    return _finish(eng, results, stats, on_error, return_stats)
+
+
+def _finish(eng, results, stats, on_error, return_stats):
+    """the searches in which a move raised, and the call's return value"""
     errs = np.nonzero(stats["status"] == _lib.BFS_MOVE_ERROR)[0]
     if len(errs):
         if on_error == "raise":
@@ -162,6 +180,35 @@ def _search_many(eng, presentations, max_nodes_to_explore, cyclically_reduce_aft
         for i in errs:
             results[int(i)] = None
     return (results, stats) if return_stats else results
+
+
+def _check_status(what, status, g0=0):
+    bad = np.nonzero(status < 0)[0]
+    if len(bad):  # validated arguments cannot get here: a full table or a kernel fault
+        raise _lib.ACXError(f"{what}: searches {(bad + g0).tolist()} ended with status {status[bad].tolist()}")
+
+
+def _read_results(eng, lib, h, dev, stream, g0, status, plen, results):
+    """status and path_len (device tensors) of the group's finished searches: the paths are read
+    back and results[g0 + i] is set for every search whose status returns one -> status on the host"""
+    n = len(status)
+    offsets = torch.cumsum(plen, 0) - plen
+    plen_h = plen.cpu().numpy()  # (waits for the searches)
+    total = int(plen_h.sum())
+    acts = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    tots = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    if total:
+        _lib.check(eng.fn(lib, "paths")(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), total, stream),
+                   f"{eng.prefix}_paths")
+    status_h = status.cpu().numpy()
+    acts_h, tots_h = acts.cpu().tolist(), tots.cpu().tolist()
+    off = 0
+    for i in range(n):
+        k = int(plen_h[i])
+        if status_h[i] in eng.path_statuses:
+            results[g0 + i] = (bool(status_h[i] == _lib.BFS_FOUND), list(zip(acts_h[off:off + k], tots_h[off:off + k])))
+        off += k
+    return status_h
 
 
 def _run_group(eng, lib, dev, L, cyclical, states, budgets, n_cap, cap, g0, stats, results):
@@ -177,29 +224,9 @@ def _run_group(eng, lib, dev, L, cyclical, states, budgets, n_cap, cap, g0, stat
         _lib.check(eng.fn(lib, "run")(h, st.data_ptr(), bd.data_ptr(), n, status.data_ptr(), nodes.data_ptr(),
                                       parents.data_ptr(), min_len.data_ptr(), plen.data_ptr(), stream),
                    f"{eng.prefix}_run")
-        ends = torch.cumsum(plen, 0)
-        offsets = ends - plen
-        plen_h = plen.cpu().numpy()  # (waits for the searches)
-        total = int(plen_h.sum())
-        acts = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        tots = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        if total:
-            _lib.check(eng.fn(lib, "paths")(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), total, stream),
-                       f"{eng.prefix}_paths")
-        status_h = status.cpu().numpy()
+        status_h = _read_results(eng, lib, h, dev, stream, g0, status, plen, results)
         stats["status"][g0:g0 + n] = status_h
         stats["nodes"][g0:g0 + n] = nodes.cpu().numpy()
         stats["parents"][g0:g0 + n] = parents.cpu().numpy()
         stats["min_length"][g0:g0 + n] = min_len.cpu().numpy()
-        acts_h, tots_h = acts.cpu().tolist(), tots.cpu().tolist()
-    bad = np.nonzero(status_h < 0)[0]
-    if len(bad):  # validated rows and budgets cannot get here: a full table or a kernel fault
-        raise _lib.ACXError(f"{eng.prefix}_run: searches {(bad + g0).tolist()} ended with status "
-                            f"{status_h[bad].tolist()}")
-    off = 0
-    for i in range(n):
-        k = int(plen_h[i])
-        if status_h[i] in eng.path_statuses:
-            results[g0 + i] = (bool(status_h[i] == _lib.BFS_FOUND),
-                               list(zip(acts_h[off:off + k], tots_h[off:off + k])))
-        off += k
+    _check_status(f"{eng.prefix}_run", status_h, g0)

@@ -1,14 +1,16 @@
-// acx_batch.h -- the frame of the batched engines (acx_mbfs.hip, acx_mgreedy.hip): one workgroup
-// owns one search, from its root to its verdict, on a private slice of each of the handle's arrays.
-// An engine adds what happens between the root and the verdict (mbfs: a round of 64 parents;
-// mgreedy: a pop off its heap) and a description of itself (`Engine`, below); everything here is
-// the same for both:
+// acx_batch.h -- the frame of the batched engines (acx_mbfs.hip, acx_mgreedy.hip, acx_beam.hip): one
+// workgroup owns one search, from its root to its verdict, on a private slice of each of the
+// handle's arrays.  An engine adds what happens between the root and the verdict (mbfs: rounds of
+// 64 parents, acx_round.h; beam: the same rounds over its beam, a step per launch with the caller's
+// scorer between; mgreedy: a pop off its heap) and a description of itself (`Engine`, below);
+// everything here is the same for all three:
 //   device  the table view (workgroup-scope reads: only the owning workgroup touches a search's
 //           memory, and a round / pop code means another child a round later, so no stale value
 //           may be read), the root (packed, checked, refused or stored as node 0), the rewrite of a
 //           survivor's table entry, the result record, the path reader;
-//   host    the handle behind the five C functions of an engine (include/acx.h: _bytes, _create,
-//           _run, _paths, _destroy), sized, allocated and freed from the engine's one list of arrays.
+//   host    the handle behind the C functions of an engine (include/acx.h: _bytes, _create, _run
+//           -- beam: its step calls instead --, _paths, _destroy), sized, allocated and freed from
+//           the engine's one list of arrays.
 // A handle is reusable: table entries carry the run's epoch (visited::next_epoch), and every other
 // array is written before it is read.
 #pragma once
@@ -182,10 +184,13 @@ __device__ __forceinline__ int64_t path_depth(const uint32_t* meta, int64_t v, i
 }
 
 // The reference's path of every search whose status is in `with_path` (bit s: status s): thread
-// per search, written at offsets[q]: [(-1, total0)] + the edges to end_node + (last_act, last_tot).
-// A node's depth is read from a.depth, or, without one, counted along meta.
-static __global__ __launch_bounds__(TPB) void path_kernel(Args a, uint32_t with_path, int64_t n, const int64_t* offsets,
-                                                          int32_t* actions, int32_t* totals, int64_t out_cap) {
+// per search, written at offsets[q]: [(-1, total0)] (root_entry: the searches of breadth_first.py
+// and greedy.py start their paths with it, value_guided_search.py's do not) + the edges to
+// end_node + (last_act, last_tot).  A node's depth is read from a.depth, or, without one, counted
+// along meta.
+static __global__ __launch_bounds__(TPB) void path_kernel(Args a, uint32_t with_path, bool root_entry, int64_t n,
+                                                          const int64_t* offsets, int32_t* actions, int32_t* totals,
+                                                          int64_t out_cap) {
     const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
     if (q >= n) return;
     const Res r = a.res[q];
@@ -194,27 +199,34 @@ static __global__ __launch_bounds__(TPB) void path_kernel(Args a, uint32_t with_
     const uint64_t* store = a.store + q * a.rows * a.kw;
     const uint32_t* meta = a.meta + q * a.rows;
     const int64_t d = a.depth ? (int64_t)(a.depth + q * a.rows)[r.end_node] : path_depth(meta, r.end_node, a.rows);
-    const int64_t off = offsets[q];
-    if (off < 0 || off + d + 2 > out_cap) return;
-    actions[off] = -1;
-    totals[off] = key_total(store, a.L);
-    int64_t pos = off + d;
-    for (int64_t i = r.end_node; i != 0 && i < a.rows && pos > off; i = meta[i] >> 4, --pos) {
+    int64_t off = offsets[q];
+    if (off < 0 || off + d + 1 + root_entry > out_cap) return;
+    if (root_entry) {
+        actions[off] = -1;
+        totals[off] = key_total(store, a.L);
+        ++off;
+    }
+    int64_t pos = off + d - 1;
+    for (int64_t i = r.end_node; i != 0 && i < a.rows && pos >= off; i = meta[i] >> 4, --pos) {
         actions[pos] = (int32_t)(meta[i] & 15u);
         totals[pos] = key_total(store + i * a.kw, a.L);
     }
-    actions[off + d + 1] = r.last_act;
-    totals[off + d + 1] = r.last_tot;
+    actions[off + d] = r.last_act;
+    totals[off + d] = r.last_tot;
 }
 
 // ---------------------------------------------------------------------------------------------
 // host: the handle of an engine E, which states
 //   Args                     its kernel's arguments, derived from batch::Args;
-//   WITH_PATH                the statuses whose searches return a path (bit s: status s);
+//   WITH_PATH, ROOT_ENTRY    the statuses whose searches return a path (bit s: status s), and
+//                            whether a path starts with the root's (-1, total0);
 //   rows_for(B), buckets_for(B)   node rows and table buckets per search at budgets up to B;
 //   arrays(a, f)             its arrays, once: f(pointer in a, bytes per search, zeroed at create)
 //                            for each -- _bytes, _create and the destructor all go through it;
-//   launch<NW>(a, n, st)     its kernel over n searches.
+//   launch<NW>(a, n, st)     its kernel over n searches, for run() (beam, whose step is several
+//                            calls, has none and starts its kernels itself after new_epoch()).
+// An engine with shape parameters of its own (beam: max_width) sets them in its Args, calls
+// shape() and then bytes_of() / create_from(); the others call bytes() / create().
 // ---------------------------------------------------------------------------------------------
 template <class E>
 struct Handle {
@@ -242,19 +254,24 @@ static bool shape(typename E::Args& a, int32_t L, int64_t B, int32_t cyclical) {
     return true;
 }
 
+// bytes per search of a shaped handle
 template <class E>
-static int64_t bytes(int32_t L, int64_t B) {
-    typename E::Args a{};
-    if (!shape<E>(a, L, B, 0)) return ACX_E_ARG;
+static int64_t bytes_of(typename E::Args a) {
     size_t sum = 0;
     E::arrays(a, [&](auto*&, size_t b, bool) { sum += b; });
     return (int64_t)sum;
 }
 
 template <class E>
-static void* create(int32_t L, int64_t n_searches, int64_t B, int32_t cyclical) {
+static int64_t bytes(int32_t L, int64_t B) {
     typename E::Args a{};
-    if (n_searches < 1 || n_searches > MAX_SEARCHES || !shape<E>(a, L, B, cyclical)) return nullptr;
+    return shape<E>(a, L, B, 0) ? bytes_of<E>(a) : ACX_E_ARG;
+}
+
+// a handle of shape `a` for n_searches searches, or null
+template <class E>
+static void* create_from(const typename E::Args& a, int64_t n_searches) {
+    if (n_searches < 1 || n_searches > MAX_SEARCHES) return nullptr;
     Handle<E>* S = new (std::nothrow) Handle<E>();
     if (!S) return nullptr;
     S->a = a;
@@ -271,6 +288,18 @@ static void* create(int32_t L, int64_t n_searches, int64_t B, int32_t cyclical) 
         return nullptr;
     }
     return S;
+}
+
+template <class E>
+static void* create(int32_t L, int64_t n_searches, int64_t B, int32_t cyclical) {
+    typename E::Args a{};
+    return shape<E>(a, L, B, cyclical) ? create_from<E>(a, n_searches) : nullptr;
+}
+
+// a run's epoch for the handle's tables (visited::next_epoch); false: the launch failed
+template <class E>
+static bool new_epoch(Handle<E>* S, hipStream_t st) {
+    return visited::next_epoch(S->epoch, S->a.table, (size_t)S->n_cap * S->a.nb * BUCKET * 8, st, S->a.ep);
 }
 
 template <class E>
@@ -291,7 +320,7 @@ static int run(void* h, const int32_t* states, const int64_t* budgets, int64_t n
     if (n == 0) return ACX_OK;
     hipStream_t st = (hipStream_t)stream;
     typename E::Args& a = S->a;
-    if (!visited::next_epoch(S->epoch, a.table, (size_t)S->n_cap * a.nb * BUCKET * 8, st, a.ep)) return ACX_E_LAUNCH;
+    if (!new_epoch(S, st)) return ACX_E_LAUNCH;
     a.states = states;
     a.budgets = budgets;
     a.status = status;
@@ -310,7 +339,7 @@ static int paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, i
     if (!S || !offsets || !actions || !totals || n < 0 || n > S->n_cap || cap < 0) return ACX_E_ARG;
     if (n == 0) return ACX_OK;
     path_kernel<<<dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream>>>(
-        S->a, E::WITH_PATH, n, offsets, actions, totals, cap);
+        S->a, E::WITH_PATH, E::ROOT_ENTRY, n, offsets, actions, totals, cap);
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 

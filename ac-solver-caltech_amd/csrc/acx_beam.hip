@@ -25,15 +25,15 @@
 // Bytes per search (acx_beam_bytes):
 //   8 kw B + 4 B + 64 ceil((B + 779) / 4) + 4 max_width + 140 [+ 6144 kw when L > 64].
 //
-// beam_expand_kernel<NW>: a step is ceil(beam / 64) passes, each a round of acx_mbfs.hip over the
-// next P <= 64 beam entries -- expand, insert, decide, commit, with a barrier between.  The
-// differences: the parents are read through the beam; the cut is the child that holds the
-// (max_nodes - total_nodes)-th survivor in sequential order, found from the per-parent survivor
-// masks, and only survivors up to it are committed; a pass is committed before the next begins, so
-// a later pass meets the earlier ones' children as nodes.  A round code is n + s with n the node
-// count when its pass began: every holder of a pass without a verdict is recoded to its node index
-// (< the next pass's n) at commit, and a pass with a verdict (cut included) is the search's last
-// insert, so no round code is ever read as a node index.
+// beam_expand_kernel<NW>: a step is ceil(beam / 64) passes, each a round (acx_round.h) over the
+// next P <= 64 beam entries, read through the beam.  Its decide finds the cut: the child that holds
+// the (max_nodes - total_nodes)-th survivor in sequential order, from the per-parent survivor
+// masks, and only survivors up to it are committed (a pass with a budget verdict still commits).
+// A pass is committed before the next begins, so a later pass meets the earlier ones' children as
+// nodes.  A round code is n + s with n the node count when its pass began: every holder of a pass
+// without a verdict is recoded to its node index (< the next pass's n) at commit, and a pass with
+// a verdict (cut included) is the search's last insert, so no round code is ever read as a node
+// index.
 // beam_select_kernel<CAP>: the candidates' (score key, index) words (acx_beam_key.h) are sorted in
 // LDS by a bitonic network over the next power of two, CAP = 1024, 4096 or 16384 words by the
 // handle's max_width (8, 32, 128 KiB of LDS: the widest class holds one workgroup per CU, which is
@@ -42,7 +42,7 @@
 // max_width / 64, probes by nb, the path walk by the node count.
 //
 // Registers and LDS (hipcc --offload-arch=gfx950 -O3, the kernels' metadata in --save-temps):
-//   beam_expand_kernel<1 / 2 / 3 / 4 / 8>   84 / 90 / 92 / 94 / 126 VGPRs, 18,976 / 25,120 / 31,264 /
+//   beam_expand_kernel<1 / 2 / 3 / 4 / 8>   82 / 88 / 90 / 92 / 126 VGPRs, 18,976 / 25,120 / 31,264 /
 //       37,408 / 6,684 B of LDS: 5, 5, 5, 4, 4 waves per SIMD, as mbfs_kernel (<2> also has 24 B of
 //       private memory per lane; the other widths have none);
 //   beam_select_kernel<1024 / 4096 / 16384>   12 / 12 / 13 VGPRs, 8,200 / 32,776 / 131,080 B of LDS.
@@ -50,23 +50,14 @@
 #include <stdint.h>
 
 #include "acx.h"
-#include "acx_moves.h"
 
-#include "acx_batch.h"
 #include "acx_beam_key.h"
-#include "acx_bfs_common.h"
-#include "acx_visited.h"
+#include "acx_round.h"
 
 namespace acx {
 namespace beam {
 
-using namespace acx::bfs;
-using batch::Buckets;
-using batch::Res;
-using visited::BUCKET;
-
-constexpr int RP = 64;       // beam entries per pass
-constexpr int RC = 12 * RP;  // children per pass
+using namespace acx::round;
 
 // a search between two launches
 struct State {
@@ -76,8 +67,7 @@ struct State {
     int32_t pad;
 };
 
-struct Args : batch::Args {
-    uint64_t* scratch;
+struct Args : round::Args {
     State* state;
     uint32_t* beam;    // (max_width) per search
     int32_t* counts;   // (n) the step's candidates per search
@@ -118,14 +108,7 @@ __global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* 
 
 template <int NW>
 __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
-    constexpr bool LDS_KEYS = NW <= 4;
-    __shared__ uint64_t kl[LDS_KEYS ? RC * (NW + 1) : 1];
-    __shared__ uint32_t slot[RC];    // table index of the entry a child holds
-    __shared__ uint16_t ctot[RC];    // child total, 0xffff: the move raised (or no such child)
-    __shared__ uint8_t cand[RC];     // the child holds its state's entry after its own probe
-    __shared__ uint8_t lost[RC];     // an earlier child of the pass took that entry
-    __shared__ uint32_t pmask[RP], pexcl[RP];
-    __shared__ uint32_t s_succ, s_err, s_min, s_over;
+    __shared__ Lds r;
     __shared__ uint32_t s_dec[3];    // verdict kind, children looked at, new nodes
 
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
@@ -138,15 +121,13 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
     uint32_t* meta = a.meta + q * a.rows;
     uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
     const uint32_t* beam = a.beam + q * a.max_width;
-    uint64_t* ck;
-    if constexpr (LDS_KEYS) ck = kl;
-    else ck = a.scratch + q * (int64_t)RC * kw;
+    uint64_t* ck = keys_of<NW>(a, q);
 
     int64_t n_nodes = S->n_nodes, steps = S->steps;
     const int64_t max_nodes = S->max_nodes;
     const int beam_n = S->beam_n;
     uint32_t running = S->running;
-    if (tid == 0) s_over = 0;
+    if (tid == 0) r.s_over = 0;
     __syncthreads();  // the state is read before thread 0 rewrites it
     if (n_nodes >= max_nodes || beam_n < 1) {  // the reference's loop condition
         if (tid == 0) finish(a, q, S, beam_n < 1 ? ACX_BFS_EXHAUSTED : ACX_BFS_BUDGET, 0, 0, n_nodes, steps, running, 0);
@@ -160,73 +141,16 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
     for (int base = 0; base < beam_n; base += RP) {
         const int P = beam_n - base < RP ? beam_n - base : RP;
         const int nch = 12 * P;
-        for (int c = tid; c < RC; c += TPB) {
-            cand[c] = 0;
-            lost[c] = 0;
-            ctot[c] = 0xffffu;
-        }
-        if (tid == 0) s_succ = s_err = NONE;
+        reset(r);
         __syncthreads();
-
-        // expand
-        {
-            uint32_t succ = NONE, err = NONE;
-            if (lane < P) {
-                PresRegs<NW> pr;
-                const int64_t pn = beam[base + lane];
-                load_key<NW>(store + (pn < a.rows ? pn : 0) * kw, kw, L, pr);
-                const bool clean = is_clean<NW>(pr.w0, pr.n0, pr.w1, pr.n1, cyc);
-#pragma unroll 1
-                for (int j = 0; j < 3; ++j) {
-                    const int act = wid * 3 + j;
-                    const uint32_t s = (uint32_t)lane * 12u + (uint32_t)act;
-                    PresRegs<NW> c;
-                    const int e = child_of<NW>(pr, clean, act, L, cyc, c);
-                    if (e != ACX_ERR_NONE) {
-                        err = min(err, s);
-                    } else {
-                        const uint32_t tot = (uint32_t)(c.n0 + c.n1);
-                        if (tot == 2) succ = min(succ, s);
-                        ctot[s] = (uint16_t)tot;
-                    }
-                    uint64_t key[NW + 1];
-                    make_key<NW>(L, c, key);
-#pragma unroll
-                    for (int k = 0; k < NW + 1; ++k)
-                        if (k < kw) ck[s * kw + k] = key[k];
-                }
-            }
-            succ = wave_min(succ);
-            err = wave_min(err);
-            if (lane == 0) {
-                if (succ != NONE) atomicMin(&s_succ, succ);
-                if (err != NONE) atomicMin(&s_err, err);
-            }
-        }
+        expand<NW>(r, ck, store, P, L, kw, cyc, [&](int p) {
+            const int64_t pn = beam[base + p];
+            return pn < a.rows ? pn : 0;
+        });
         __syncthreads();
-
-        // insert: the success / raising child ends the search, later children are not looked at
-        const uint32_t end0 = min(s_succ, s_err);
-        const uint64_t NB = (uint64_t)n_nodes;
-        for (int c = tid; c < nch; c += TPB) {
-            if ((uint32_t)c >= end0) continue;
-            const uint64_t code = NB + (uint64_t)c;
-            const Key<NW + 1> key = kload<NW + 1>(ck + c * kw, kw);
-            const visited::Outcome ins = visited::insert(
-                Buckets{table, a.nb}, a.ep, code, khash<NW + 1>(key, kw),
-                [&](uint64_t vc) {
-                    return vc < NB ? keq<NW + 1>(store + vc * kw, key, kw) : keq<NW + 1>(ck + (vc - NB) * kw, key, kw);
-                },
-                [&](uint32_t sl, uint64_t displaced) {  // a later child of the pass that held it learns it lost
-                    slot[c] = sl;
-                    const uint64_t lc = displaced - NB;
-                    if (displaced != visited::NO_CODE && lc < (uint64_t)RC) lost[lc] = 1;
-                });
-            if (ins == visited::FULL) s_over = 1;
-            cand[c] = ins == visited::HELD;
-        }
+        insert<NW>(r, ck, store, table, a, n_nodes, nch, kw);
         __syncthreads();
-        if (s_over) {  // (uniform) cannot happen at load <= 1/2
+        if (r.s_over) {  // (uniform) cannot happen at load <= 1/2
             status = ACX_MBFS_OVERFLOW;
             break;
         }
@@ -239,7 +163,7 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
 #pragma unroll
                 for (int act = 0; act < 12; ++act) {
                     const int c = lane * 12 + act;
-                    if (cand[c] && !lost[c]) m |= 1u << act;
+                    if (r.cand[c] && !r.lost[c]) m |= 1u << act;
                 }
             }
             const uint32_t cnt = __popc(m);
@@ -261,9 +185,10 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
                 }
                 cutc = 12u * (uint32_t)cutp + (uint32_t)__shfl((int)act, cutp, WAVE);
             }
-            pmask[lane] = m;
-            pexcl[lane] = x - cnt;
+            r.pmask[lane] = m;
+            r.pexcl[lane] = x - cnt;
             if (lane == 0) {
+                const uint32_t s_succ = r.s_succ, s_err = r.s_err, end0 = min(s_succ, s_err);
                 uint32_t kind = 0, looked = (uint32_t)nch;
                 if (cutb) {
                     kind = ACX_BFS_BUDGET;
@@ -275,34 +200,18 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
                 s_dec[0] = kind;
                 s_dec[1] = looked;
                 s_dec[2] = cutb ? (uint32_t)need : total;
-                s_min = NONE;
+                r.s_min = NONE;
             }
         }
         __syncthreads();
         const uint32_t kind = s_dec[0], s_end = s_dec[1], newn = s_dec[2];
 
-        // commit: the survivors (up to the cut) become nodes in sequential order
-        if (kind == 0 || kind == ACX_BFS_BUDGET) {
-            for (int c = tid; c < nch; c += TPB) {
-                const int p = c / 12, act = c - 12 * p;
-                const uint32_t m = pmask[p];
-                if (!((m >> act) & 1u)) continue;
-                const int64_t pos = n_nodes + pexcl[p] + __popc(m & ((1u << act) - 1u));
-                if (pos >= a.rows) continue;  // (never: total_nodes <= max_nodes <= rows)
-                for (int k = 0; k < kw; ++k) store[pos * kw + k] = ck[c * kw + k];
-                meta[pos] = (beam[base + p] << 4) | (uint32_t)act;
-                batch::recode_entry(table, slot[c], (uint64_t)pos);
-            }
-        }
-        {
-            uint32_t m = NONE;
-            for (int c = tid; c < nch; c += TPB)
-                if ((uint32_t)c < s_end) m = min(m, (uint32_t)ctot[c]);
-            m = wave_min(m);
-            if (lane == 0 && m != NONE) atomicMin(&s_min, m);
-        }
+        // the survivors (up to the cut) become nodes in sequential order
+        if (kind == 0 || kind == ACX_BFS_BUDGET)
+            commit<NW>(r, ck, store, meta, table, a, n_nodes, nch, kw, [&](int p) { return beam[base + p]; });
+        min_upto(r, nch, s_end);
         __syncthreads();
-        running = min(running, s_min);
+        running = min(running, r.s_min);
         n_nodes += newn;
         if (kind == ACX_BFS_FOUND || kind == ACX_BFS_MOVE_ERROR) {
             status = (int32_t)kind;
@@ -422,41 +331,17 @@ __global__ __launch_bounds__(TPB) void beam_finish_kernel(Args a, int32_t* statu
     path_len[q] = a.path_len[q];
 }
 
-// The reference's path of every found search (value_guided_search.py:87-97,497-498): thread per
-// search, written at offsets[q]: the edges to end_node + (last_act, 2), no root entry.
-__global__ __launch_bounds__(TPB) void beam_path_kernel(Args a, int64_t n, const int64_t* offsets, int32_t* actions,
-                                                        int32_t* totals, int64_t out_cap) {
-    const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (q >= n) return;
-    const Res r = a.res[q];
-    if (r.status != ACX_BFS_FOUND || r.end_node < 0 || r.end_node >= a.rows) return;
-    const uint64_t* store = a.store + q * a.rows * a.kw;
-    const uint32_t* meta = a.meta + q * a.rows;
-    const int64_t d = batch::path_depth(meta, r.end_node, a.rows);
-    const int64_t off = offsets[q];
-    if (off < 0 || off + d + 1 > out_cap) return;
-    int64_t pos = off + d - 1;
-    for (int64_t i = r.end_node; i != 0 && i < a.rows && pos >= off; i = meta[i] >> 4, --pos) {
-        actions[pos] = (int32_t)(meta[i] & 15u);
-        totals[pos] = key_total(store + i * a.kw, a.L);
-    }
-    actions[off + d] = r.last_act;
-    totals[off + d] = r.last_tot;
-}
-
 // what the handle (acx_batch.h) needs of this engine; max_width is set before arrays() is called
 struct Engine {
     using Args = beam::Args;
+    // a found search's path (value_guided_search.py:87-97,497-498): the edges + (action, 2), no root entry
+    static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND;
+    static constexpr bool ROOT_ENTRY = false;
     static int64_t rows_for(int64_t B) { return B; }
-    static uint32_t buckets_for(int64_t B) { return (uint32_t)((2 * (B + 11 + RC) + BUCKET - 1) / BUCKET); }
+    static uint32_t buckets_for(int64_t B) { return round::buckets_for(B); }
     template <class F>
     static void arrays(Args& a, F f) {
-        const size_t R = (size_t)a.rows, kw = (size_t)a.kw;
-        f(a.store, 8 * kw * R, false);
-        f(a.meta, 4 * R, false);
-        f(a.table, 8 * (size_t)BUCKET * a.nb, true);
-        f(a.res, sizeof(Res), true);
-        f(a.scratch, a.L > 64 ? 8 * kw * RC : 0, false);  // a pass's child keys where they do not stay in LDS
+        round::arrays(a, f);
         f(a.beam, 4 * (size_t)a.max_width, false);
         f(a.state, sizeof(State), true);  // (zeroed: done = 0 with no candidates before the first begin)
         f(a.counts, 4, true);
@@ -501,35 +386,16 @@ extern "C" {
 
 int64_t acx_beam_bytes(int32_t L, int64_t max_nodes_each, int32_t max_width) {
     beam::Args a{};
-    if (!beam::shape(a, L, max_nodes_each, max_width, 0)) return ACX_E_ARG;
-    size_t sum = 0;
-    beam::Engine::arrays(a, [&](auto*&, size_t b, bool) { sum += b; });
-    return (int64_t)sum;
+    return beam::shape(a, L, max_nodes_each, max_width, 0) ? batch::bytes_of<beam::Engine>(a) : ACX_E_ARG;
 }
 
 void* acx_beam_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t max_width, int32_t cyclical) {
     beam::Args a{};
-    if (n_searches < 1 || n_searches > batch::MAX_SEARCHES || !beam::shape(a, L, max_nodes_each, max_width, cyclical))
-        return nullptr;
-    Handle* S = new (std::nothrow) Handle();
-    if (!S) return nullptr;
-    S->a = a;
-    S->n_cap = n_searches;
-    const size_t n = (size_t)n_searches;
-    bool ok = true;
-    beam::Engine::arrays(S->a, [&](auto*& p, size_t b, bool zero) {
-        ok = ok && (b == 0 || (hipMalloc((void**)&p, n * b) == hipSuccess &&
-                               (!zero || hipMemset(p, 0, n * b) == hipSuccess)));
-    });
-    if (!ok) {
-        (void)hipGetLastError();
-        delete S;
-        return nullptr;
-    }
-    return S;
+    if (!beam::shape(a, L, max_nodes_each, max_width, cyclical)) return nullptr;
+    return batch::create_from<beam::Engine>(a, n_searches);
 }
 
-void acx_beam_destroy(void* h) { delete static_cast<Handle*>(h); }
+void acx_beam_destroy(void* h) { batch::destroy<beam::Engine>(h); }
 
 int acx_beam_begin(void* h, const int32_t* states, const int64_t* budgets, const int32_t* widths, int64_t n,
                    void* stream) {
@@ -539,8 +405,7 @@ int acx_beam_begin(void* h, const int32_t* states, const int64_t* budgets, const
     a.n = n;
     if (n == 0) return ACX_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (!acx::visited::next_epoch(S->epoch, a.table, (size_t)S->n_cap * a.nb * acx::visited::BUCKET * 8, st, a.ep))
-        return ACX_E_LAUNCH;
+    if (!batch::new_epoch(S, st)) return ACX_E_LAUNCH;
     a.states = states;
     a.budgets = budgets;
     acx::bfs::by_nw(a.L, beam::Begin{a, widths, st});
@@ -592,12 +457,7 @@ int acx_beam_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, in
 
 int acx_beam_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
                    void* stream) {
-    Handle* S = static_cast<Handle*>(h);
-    if (!S || !offsets || !actions || !totals || n < 0 || n > S->n_cap || cap < 0) return ACX_E_ARG;
-    if (n == 0) return ACX_OK;
-    beam::beam_path_kernel<<<dim3((unsigned)((n + acx::bfs::TPB - 1) / acx::bfs::TPB)), dim3(acx::bfs::TPB), 0,
-                             (hipStream_t)stream>>>(S->a, n, offsets, actions, totals, cap);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return batch::paths<beam::Engine>(h, n, offsets, actions, totals, cap, stream);
 }
 
 }  // extern "C"

@@ -14,73 +14,40 @@
 //   table  (nb * 8) uint64  the visited set (acx_visited.h: buckets of 8 entries), nb buckets with
 //                           8 nb >= 2 (B + 11 + 768) -- load <= 1/2 -- chosen by range reduction
 //                           of the hash (no power-of-two rounding);
-//   scratch (768, kw) uint64  only for L > 64: the round's child keys (below).
+//   scratch (768, kw) uint64  only for L > 64: the round's child keys.
 // B = max_nodes_each.  Bytes per search (acx_mbfs_bytes):
 //   8 kw B + 4 B + 64 ceil((B + 779) / 4) + 32 [+ 6144 kw when L > 64],   kw = acx_key_words(L).
 //
-// A round takes the next P <= 64 parents (nodes head .. head + P) and runs, with a barrier between:
-//   expand  lane = parent, wave w makes actions 3w..3w+2 (child_of, acx_bfs_common.h); the
-//           768 child keys go to LDS in sequential order s = 12 p + a (L <= 64: at most 30 KiB;
-//           above that 54 KiB of LDS would halve the workgroups per CU, so they go to the
-//           search's scratch in HBM); first success and first raising child by LDS atomicMin;
-//   insert  thread per child s below the first success / raising child: visited::insert; a code
-//           below n (the nodes before the round) names a stored node, a code n + s a child of this
-//           round, so the full key is compared in the store or in the round's keys.  The first
-//           occurrence holds the entry, the child it replaced is told (`lost`).  A probe that has
-//           walked all nb buckets sets the overflow status;
-//   decide  wave 0: survivors per parent, their prefix sum, the first parent after which
-//           len(tree_nodes) >= max_nodes, and the reference's verdict for the round
-//           (chunk_verdict, acx_bfs_verdict.h: raising child / success / budget cut, the earliest
-//           in sequential order; otherwise the next round, or queue exhaustion);
-//   commit  (no verdict yet) the survivors' keys are appended in (parent, action) order with
-//           their meta word, and each survivor's table entry is rewritten from its round code to
-//           its node index; the running minimum takes the child totals up to the ending event.
-// A round with a verdict appends nothing, so a search holds fewer than max_nodes nodes and the
-// store needs B rows.  Every loop is bounded: rounds by max_nodes (each expands >= 1 of fewer than
-// max_nodes nodes), probes by nb, the path walks by the node count.
+// A round (acx_round.h) takes the next P <= 64 parents, nodes head .. head + P.  Its decide is
+// wave 0's: survivors per parent, their prefix sum, the first parent after which len(tree_nodes) >=
+// max_nodes, and the reference's verdict for the round (chunk_verdict, acx_bfs_verdict.h: raising
+// child / success / budget cut, the earliest in sequential order; otherwise the next round, or
+// queue exhaustion).  A round with a verdict appends nothing, so a search holds fewer than
+// max_nodes nodes and the store needs B rows.  Every loop is bounded: rounds by max_nodes (each
+// expands >= 1 of fewer than max_nodes nodes), probes by nb, the path walks by the node count.
 //
 // The frame around the round -- the root and its refusal statuses, the table view with its
 // workgroup-scope reads (node codes in acx_bfs.hip are permanent, which is why its plain bucket
 // loads are safe there; a round code here means another node a round later), the result record,
-// the path reader and the reusable handle behind acx_mbfs_* -- is acx_batch.h, shared with
-// acx_mgreedy.hip.  The insert call stays here: as a shared routine it cost mgreedy_kernel<8>
-// 14 VGPRs (95 -> 109) in every shape tried.
+// the path reader and the reusable handle behind acx_mbfs_* -- is acx_batch.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "acx.h"
-#include "acx_moves.h"
 
-#include "acx_batch.h"
-#include "acx_bfs_common.h"
 #include "acx_bfs_verdict.h"
-#include "acx_visited.h"
+#include "acx_round.h"
 
 namespace acx {
 namespace mbfs {
 
-using namespace acx::bfs;
-using batch::Buckets;
-using batch::Res;
-using visited::BUCKET;
+using namespace acx::round;
 
-constexpr int RP = 64;          // parents per round
-constexpr int RC = 12 * RP;     // children per round
-
-struct Args : batch::Args {
-    uint64_t* scratch;
-};
+struct Args : round::Args {};
 
 template <int NW>
 __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
-    constexpr bool LDS_KEYS = NW <= 4;
-    __shared__ uint64_t kl[LDS_KEYS ? RC * (NW + 1) : 1];
-    __shared__ uint32_t slot[RC];    // table index of the entry a child holds
-    __shared__ uint16_t ctot[RC];    // child total, 0xffff: the move raised (or no such child)
-    __shared__ uint8_t cand[RC];     // the child holds its state's entry after its own probe
-    __shared__ uint8_t lost[RC];     // an earlier child of the round took that entry
-    __shared__ uint32_t pmask[RP], pexcl[RP];
-    __shared__ uint32_t s_succ, s_err, s_min, s_over;
+    __shared__ Lds r;
     __shared__ uint32_t s_dec[4];    // verdict kind, children looked at, last parent, new nodes
 
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
@@ -90,11 +57,9 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
     uint64_t* store = a.store + q * a.rows * kw;
     uint32_t* meta = a.meta + q * a.rows;
     uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
-    uint64_t* ck;
-    if constexpr (LDS_KEYS) ck = kl;
-    else ck = a.scratch + q * (int64_t)RC * kw;
+    uint64_t* ck = keys_of<NW>(a, q);
 
-    if (tid == 0) s_over = 0;
+    if (tid == 0) r.s_over = 0;
     const batch::Root root = batch::root_setup<TPB, NW>(a, q, store, meta, table);
     if (root.refused) return;
     const int64_t max_nodes = root.max_nodes;
@@ -107,72 +72,13 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
     for (int64_t round = 0; round <= max_nodes; ++round) {
         const int P = (int)(n_nodes - head < RP ? n_nodes - head : RP);
         const int nch = 12 * P;
-        for (int c = tid; c < RC; c += TPB) {
-            cand[c] = 0;
-            lost[c] = 0;
-            ctot[c] = 0xffffu;
-        }
-        if (tid == 0) s_succ = s_err = NONE;
+        reset(r);
         __syncthreads();
-
-        // expand
-        {
-            uint32_t succ = NONE, err = NONE;
-            if (lane < P) {
-                PresRegs<NW> pr;
-                load_key<NW>(store + (head + lane) * kw, kw, L, pr);
-                const bool clean = is_clean<NW>(pr.w0, pr.n0, pr.w1, pr.n1, cyc);
-#pragma unroll 1
-                for (int j = 0; j < 3; ++j) {
-                    const int act = wid * 3 + j;
-                    const uint32_t s = (uint32_t)lane * 12u + (uint32_t)act;
-                    PresRegs<NW> c;
-                    const int e = child_of<NW>(pr, clean, act, L, cyc, c);
-                    if (e != ACX_ERR_NONE) {
-                        err = min(err, s);
-                    } else {
-                        const uint32_t tot = (uint32_t)(c.n0 + c.n1);
-                        if (tot == 2) succ = min(succ, s);
-                        ctot[s] = (uint16_t)tot;
-                    }
-                    uint64_t key[NW + 1];
-                    make_key<NW>(L, c, key);
-#pragma unroll
-                    for (int k = 0; k < NW + 1; ++k)
-                        if (k < kw) ck[s * kw + k] = key[k];
-                }
-            }
-            succ = wave_min(succ);
-            err = wave_min(err);
-            if (lane == 0) {
-                if (succ != NONE) atomicMin(&s_succ, succ);
-                if (err != NONE) atomicMin(&s_err, err);
-            }
-        }
+        expand<NW>(r, ck, store, P, L, kw, cyc, [&](int p) { return head + p; });
         __syncthreads();
-
-        // insert: the success / raising child ends the search, later children are not looked at
-        const uint32_t end0 = min(s_succ, s_err);
-        const uint64_t NB = (uint64_t)n_nodes;
-        for (int c = tid; c < nch; c += TPB) {
-            if ((uint32_t)c >= end0) continue;
-            const uint64_t code = NB + (uint64_t)c;
-            const Key<NW + 1> key = kload<NW + 1>(ck + c * kw, kw);
-            const visited::Outcome ins = visited::insert(
-                Buckets{table, a.nb}, a.ep, code, khash<NW + 1>(key, kw),
-                [&](uint64_t vc) {
-                    return vc < NB ? keq<NW + 1>(store + vc * kw, key, kw) : keq<NW + 1>(ck + (vc - NB) * kw, key, kw);
-                },
-                [&](uint32_t sl, uint64_t displaced) {  // a later child of the round that held it learns it lost
-                    slot[c] = sl;
-                    const uint64_t lc = displaced - NB;
-                    if (displaced != visited::NO_CODE && lc < (uint64_t)RC) lost[lc] = 1;
-                });
-            if (ins == visited::FULL) s_over = 1;
-            cand[c] = ins == visited::HELD;
-        }
+        insert<NW>(r, ck, store, table, a, n_nodes, nch, kw);
         __syncthreads();
-        if (s_over) break;  // (uniform) cannot happen at load <= 1/2
+        if (r.s_over) break;  // (uniform) cannot happen at load <= 1/2
 
         // decide
         if (wid == 0) {
@@ -181,52 +87,35 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
 #pragma unroll
                 for (int act = 0; act < 12; ++act) {
                     const int c = lane * 12 + act;
-                    if (cand[c] && !lost[c]) m |= 1u << act;
+                    if (r.cand[c] && !r.lost[c]) m |= 1u << act;
                 }
             }
             const uint32_t cnt = __popc(m);
             const uint32_t x = wave_incl_sum(cnt, lane);
-            pmask[lane] = m;
-            pexcl[lane] = x - cnt;
+            r.pmask[lane] = m;
+            r.pexcl[lane] = x - cnt;
             const uint32_t total = __shfl(x, WAVE - 1, WAVE);
             // the first parent after which len(tree_nodes) >= max_nodes
             const unsigned long long cutb = __ballot(lane < P && n_nodes + (int64_t)x >= max_nodes);
             const uint32_t cutp = cutb ? (uint32_t)__builtin_ctzll(cutb) : NONE;
             const uint32_t at_cut = __shfl(x, cutb ? (int)cutp : 0, WAVE);
-            const Verdict v = chunk_verdict(s_succ, s_err, cutp, (uint32_t)P);
+            const Verdict v = chunk_verdict(r.s_succ, r.s_err, cutp, (uint32_t)P);
             if (lane == 0) {
                 s_dec[0] = (uint32_t)v.kind;
                 s_dec[1] = v.looked;
                 s_dec[2] = v.last_p;
                 s_dec[3] = v.kind == ACX_BFS_BUDGET ? at_cut : total;
-                s_min = NONE;
+                r.s_min = NONE;
             }
         }
         __syncthreads();
         const uint32_t kind = s_dec[0], s_end = s_dec[1], last_p = s_dec[2], newn = s_dec[3];
 
-        // commit
-        if (kind == 0) {
-            for (int c = tid; c < nch; c += TPB) {
-                const int p = c / 12, act = c - 12 * p;
-                const uint32_t m = pmask[p];
-                if (!((m >> act) & 1u)) continue;
-                const int64_t pos = n_nodes + pexcl[p] + __popc(m & ((1u << act) - 1u));
-                if (pos >= a.rows) continue;  // (never: a round without a verdict ends below max_nodes)
-                for (int k = 0; k < kw; ++k) store[pos * kw + k] = ck[c * kw + k];
-                meta[pos] = ((uint32_t)(head + p) << 4) | (uint32_t)act;
-                batch::recode_entry(table, slot[c], (uint64_t)pos);
-            }
-        }
-        {
-            uint32_t m = NONE;
-            for (int c = tid; c < nch; c += TPB)
-                if ((uint32_t)c < s_end) m = min(m, (uint32_t)ctot[c]);
-            m = wave_min(m);
-            if (lane == 0 && m != NONE) atomicMin(&s_min, m);
-        }
+        if (kind == 0)
+            commit<NW>(r, ck, store, meta, table, a, n_nodes, nch, kw, [&](int p) { return (uint32_t)(head + p); });
+        min_upto(r, nch, s_end);
         __syncthreads();
-        running = min(running, s_min);
+        running = min(running, r.s_min);
         if (kind != 0) {
             parents += (int64_t)last_p + 1;
             n_nodes += newn;
@@ -257,17 +146,11 @@ __global__ __launch_bounds__(TPB) void mbfs_kernel(Args a) {
 struct Engine {
     using Args = mbfs::Args;
     static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND;
+    static constexpr bool ROOT_ENTRY = true;
     static int64_t rows_for(int64_t B) { return B; }
-    static uint32_t buckets_for(int64_t B) { return (uint32_t)((2 * (B + 11 + RC) + BUCKET - 1) / BUCKET); }
+    static uint32_t buckets_for(int64_t B) { return round::buckets_for(B); }
     template <class F>
-    static void arrays(Args& a, F f) {
-        const size_t R = (size_t)a.rows, kw = (size_t)a.kw;
-        f(a.store, 8 * kw * R, false);
-        f(a.meta, 4 * R, false);
-        f(a.table, 8 * (size_t)BUCKET * a.nb, true);
-        f(a.res, sizeof(Res), true);
-        f(a.scratch, a.L > 64 ? 8 * kw * RC : 0, false);  // the round's child keys where they do not stay in LDS
-    }
+    static void arrays(Args& a, F f) { round::arrays(a, f); }
     template <int NW>
     static void launch(const Args& a, int64_t n, hipStream_t st) {
         mbfs_kernel<NW><<<dim3((unsigned)n), dim3(TPB), 0, st>>>(a);

@@ -347,6 +347,7 @@ __global__ __launch_bounds__(GT) void mgreedy_kernel(Args a) {
 struct Engine {
     using Args = mgreedy::Args;
     static constexpr uint32_t WITH_PATH = mgreedy::WITH_PATH;
+    static constexpr bool ROOT_ENTRY = true;
     static int64_t rows_for(int64_t B) { return B + OVERSHOOT; }
     static uint32_t buckets_for(int64_t B) { return (uint32_t)((2 * (rows_for(B) + 12) + BUCKET - 1) / BUCKET); }
     template <class F>

@@ -67,8 +67,9 @@ def _run(lib, prefix, h, states, budgets):
     return out
 
 
-def _check_search(out, i, want):
-    got = {k: int(out[k][i]) for k in ("status", "nodes", "parents", "min_length")}
+def _check_search(out, i, want, keys=("status", "nodes", "parents", "min_length")):
+    """search i of _run's (or test_gpu_beam_many._drive's) output against a yardstick's result"""
+    got = {k: int(out[k][i]) for k in keys}
     assert got == {k: want[k] for k in got}, (i, got, want)
     k = len(want["path"])
     assert out["path_len"][i] == k, (i, want)

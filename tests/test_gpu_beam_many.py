@@ -6,19 +6,15 @@ float32 values are exact, every search gives the reference's beam_search result
 CPU by test_beam_cpu.py).  A call has one scorer, so the fixture's records are grouped by
 (L, flag, scorer)."""
 import functools
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import beam_yardstick as Y
-import weak_hash_common as WH
-from conftest import REPO
 from many_common import AK2, _dataset_rows, _load, _norm, _same, _scrambled
+from test_gpu_batch_refusals import SENTINEL, _rows
+from test_gpu_batch_refusals import _check_search as _refusals_check_search
 
 pytestmark = pytest.mark.gpu
 
@@ -272,26 +268,22 @@ def _drive(lib, h, states, budgets, widths, L, scorer="S0"):
             assert lib.acx_beam_select(h, y.data_ptr(), M, stream) == 0
         else:
             raise AssertionError("the searches did not end")
-        status, min_len = (torch.full((n,), -77, dtype=torch.int32, device=DEV) for _ in range(2))
-        nodes, steps, plen = (torch.full((n,), -77, dtype=torch.int64, device=DEV) for _ in range(3))
+        status, min_len = (torch.full((n,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(2))
+        nodes, steps, plen = (torch.full((n,), SENTINEL, dtype=torch.int64, device=DEV) for _ in range(3))
         assert lib.acx_beam_finish(h, status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(),
                                    plen.data_ptr(), stream) == 0
         out = dict(status=status.cpu().numpy(), nodes=nodes.cpu().numpy(), steps=steps.cpu().numpy(),
                    min_length=min_len.cpu().numpy(), path_len=plen.cpu().numpy())
         stride = int(out["path_len"].max()) + 3
         offsets = torch.arange(n, dtype=torch.int64, device=DEV) * stride
-        acts, tots = (torch.full((n * stride,), -77, dtype=torch.int32, device=DEV) for _ in range(2))
+        acts, tots = (torch.full((n * stride,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(2))
         assert lib.acx_beam_paths(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), n * stride, stream) == 0
         out["acts"], out["tots"] = acts.cpu().numpy().reshape(n, stride), tots.cpu().numpy().reshape(n, stride)
     return out
 
 
 def _check_search(out, i, y):
-    assert (out["status"][i], out["nodes"][i], out["steps"][i]) == (y["status"], y["nodes"], y["steps"]), i
-    k = len(y["path"])
-    assert out["path_len"][i] == k, i
-    assert [list(e) for e in zip(out["acts"][i][:k].tolist(), out["tots"][i][:k].tolist())] == y["path"], i
-    assert (out["acts"][i][k:] == -77).all() and (out["tots"][i][k:] == -77).all(), i
+    _refusals_check_search(out, i, y, ("status", "nodes", "steps"))
 
 
 @pytest.mark.parametrize("L", [13, 36])
@@ -300,7 +292,6 @@ def test_refused_searches_through_the_c_abi(L):
     handle's and for a width outside [1, max_width]: all-zero outputs, no path, the other searches
     undisturbed, nothing left behind for the handle's next run"""
     from acx import _lib
-    from test_gpu_batch_refusals import _rows
     lib = _lib.load()
     CAP, WCAP = 64, 8
     batch, valid = _rows(L)  # rows 1 .. 4 outside the domain, rows 0, 5, 6 the same valid row
@@ -316,7 +307,7 @@ def test_refused_searches_through_the_c_abi(L):
                 _lib.MBFS_OVERFLOW, _lib.MBFS_OVERFLOW, 0]
         for i, w in enumerate(want):
             if w < 0:
-                assert out["status"][i] == w and (out["acts"][i] == -77).all(), i
+                assert out["status"][i] == w and (out["acts"][i] == SENTINEL).all(), i
                 assert (out["nodes"][i], out["steps"][i], out["min_length"][i], out["path_len"][i]) == (0, 0, 0, 0), i
             else:
                 _check_search(out, i, Y.beam(batch[i], "S0", widths[i], budgets[i]))
@@ -328,25 +319,3 @@ def test_refused_searches_through_the_c_abi(L):
         assert any(y["ok"] and len(y["path"]) >= 2 for y in ys)  # paths are written and walked
     finally:
         lib.acx_beam_destroy(h)
-
-
-def test_weak_hash_run_in_a_process_of_its_own(tmp_path):
-    """AK(3), S0, W = 50 through libacx_weakhash.so (8 hash classes: every probe meets entries of
-    other states with its fingerprint): the results are those of the shipped library"""
-    job = dict(pres=[_pad(AK3, 18).tolist()], scorer="S0", W=50, budget=3000, cyc=False)
-    with open(tmp_path / "in.json", "w") as f:
-        json.dump(job, f)
-    env = dict(os.environ, ACX_LIB=WH.variant())
-    try:
-        r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "beam_weak_hash_child.py"), str(tmp_path)],
-                           env=env, capture_output=True, text=True, timeout=300)
-    except subprocess.TimeoutExpired as e:
-        raise WH.ChildDied(f"timeout: {str(e.stderr)[-2000:]}") from None
-    if r.returncode < 0 or r.returncode in WH.FATAL:
-        raise WH.ChildDied(f"exit code {r.returncode}: {r.stderr[-2000:]}")
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    got = json.loads(r.stdout.strip().splitlines()[-1])
-    WH.check_classes(got["nodes"][0], got["classes"][0], "beam AK3")
-    res, st = _many(np.array(job["pres"], np.int32), "S0", 50, 3000)
-    assert got["res"] == res and got["st"] == {k: v.tolist() for k, v in st.items()}
-    assert st["nodes"][0] == got["nodes"][0] >= 512

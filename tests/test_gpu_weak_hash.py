@@ -6,7 +6,7 @@ other states with its own fingerprint at every insert (false fingerprint matches
 compare decides), a chunk's lanes claim along that one chain, and stale entries of earlier epochs
 lie anywhere in it (tests/test_weak_hash_cpu.py pins those properties of the hash).  The searches
 must not change: the expected values are the reference's recorded runs (tests/golden), the
-yardsticks (tests/bfs_yardstick.py, tests/greedy_yardstick.py) and the same calls made in this
+yardsticks (tests/bfs_yardstick.py, tests/greedy_yardstick.py, tests/beam_yardstick.py) and the same calls made in this
 process through libacx.so -- never the variant's.
 
 The variant cannot share a process with libacx.so: each test hands its calls to one fresh child
@@ -25,6 +25,7 @@ import torch
 
 import bfs_yardstick as YB
 import greedy_yardstick as YG
+import test_gpu_beam_many as TBM
 import test_gpu_bfs_many as TB
 import test_gpu_greedy_many as TG
 from conftest import GOLDEN
@@ -167,7 +168,7 @@ def test_device_bfs(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------
-# the batched engines (csrc/acx_mbfs.hip, csrc/acx_mgreedy.hip)
+# the batched engines (csrc/acx_mbfs.hip, csrc/acx_mgreedy.hip, csrc/acx_beam.hip)
 # ---------------------------------------------------------------------------------------------
 def _check_many(answer, part, tag):
     """a call's answer against the yardstick's results y of its searches [(presentation, y)]"""
@@ -249,6 +250,17 @@ def test_greedy_many(tmp_path):
         _check_many(out[i], [(p[0], p[2]) for p in part], ("greedy_many", L, cyc))
     assert out[-1]["nodes"] == big["nodes"] >= BATCH_CAP
     _report("greedy_many", f"the largest dataset search (budget {BATCH_CAP})", big["nodes"], out[-1]["classes"])
+
+
+def test_beam_many(tmp_path):
+    """AK(3), S0, W = 50: the results are those of the shipped library"""
+    call = dict(op="beam_many", pres=[TBM._pad(TBM.AK3, 18).tolist()], scorer="S0", W=50, budget=3000, cyc=False)
+    out, _ = _job("beam_many", [call], tmp_path, timeout=300)
+    got = out[0]
+    _report("beam_many", "AK(3) L=18 W=50", got["nodes"][0], got["classes"][0])
+    res, st = TBM._many(np.array(call["pres"], np.int32), "S0", 50, 3000)
+    assert got["res"] == res and got["st"] == {k: v.tolist() for k, v in st.items()}
+    assert st["nodes"][0] == got["nodes"][0] >= 512
 
 
 # ---------------------------------------------------------------------------------------------

@@ -115,6 +115,25 @@ class Ops:
         import acx
         return self._many(acx.greedy_search_many, c)
 
+    def beam_many(self, i, c):
+        """the search's result and stats, and over its nodes (the yardstick's, packed on the CPU)
+        their count and the number of distinct key hashes"""
+        import acx
+        import beam_yardstick as Y
+        from weak_hash_common import pack_keys_np
+        pres = np.array(c["pres"], np.int32)
+        L = pres.shape[1] // 2
+        res, st = acx.beam_search_many(pres, Y.SCORERS[c["scorer"]][1], beam_width=c["W"], max_nodes_to_explore=c["budget"],
+                                       cyclically_reduce_after_moves=c["cyc"], device=self.dev, return_stats=True,
+                                       on_error="return")
+        out = {"res": [None if r is None else [bool(r[0]), _path(r[1])] for r in res],
+               "st": {k: v.tolist() for k, v in st.items()}, "nodes": [], "classes": []}
+        for p in pres:
+            states = np.stack(Y.beam(p, c["scorer"], c["W"], c["budget"], c["cyc"])["states"])
+            out["nodes"].append(int(len(states)))
+            out["classes"].append(_classes(self.lib, pack_keys_np(states, L), L)["classes"])
+        return out
+
     def sbfs(self, i, c):
         """arena_log2_cap: on a fresh workspace whose key arena starts at 2^cap records (the
         regrowth hook of csrc/acx_sbfs.hip), which is reset whatever happens"""
