@@ -8,9 +8,21 @@
 //   acx_token_ids  the SequenceValueNet input of value_guided_search.py:68-84
 //                  (_score_states_seq): letter + 2 as int64, padded with 2 to max_state_dim.
 //
+// Input domain: keys are packed keys (acx.h: letters +-1, +-2, lengths 0 .. L, either relator
+// may be empty).  States are any int32 letters; acx_features truncates each to int8 first, as
+// compute_features does (np.asarray(..., dtype=np.int8)), acx_token_ids does not (the reference's
+// _score_states_seq adds 2 to the letters as it gets them, in int64).
+//
 // Bit-exactness: counts are integers; length_ratio and max_min_ratio are computed as the
-// reference does (Python float = double division, then rounded to float32 by np.array);
-// normalisation uses IEEE float32 subtract and divide like the numpy float32 arrays.
+// reference does (Python float = double division, then rounded to float32 by np.array): for
+// lengths up to 128 that is the correctly rounded float32 quotient, so an approximate division
+// (a reciprocal and a multiply) is wrong at some pairs.  With no letters the ratio is 0.5, and
+// with an empty relator max_min_ratio is the other's length.  Normalisation is one IEEE
+// float32 subtract and one IEEE float32 divide like numpy's float32 arrays, denormal quotients
+// and overflow to +-inf included (a zero std gives numpy's inf / NaN, not tested).
+// tests/test_gpu_features.py fixes all of this bit for bit: every length pair at L = 128, 64,
+// 48, 32 and 16, the edge rows of tests/golden/features_edges.npz, a mean / std that tells the
+// 14 columns apart.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -78,9 +90,10 @@ __global__ __launch_bounds__(TPB) void features_keys_kernel(const uint64_t* keys
     write_features(k, out + i * NF, mean, stdv);
 }
 
-// features from int32 presentations (M, 2L), any int32 letters (as the reference's numpy
-// code accepts them): length = count_nonzero of the half, counts over its first `length`
-// entries
+// features from int32 presentations (M, 2L), any int32 letters: each letter is first truncated
+// to int8, as compute_features' np.asarray(presentation, dtype=np.int8) does (257 counts as x,
+// 256 as padding); then length = count_nonzero of the half, counts over its first `length`
+// entries, whatever they are (a zero inside a relator shifts the window, as in the reference)
 __global__ __launch_bounds__(TPB) void features_states_kernel(const int32_t* states, float* out, const float* mean,
                                                               const float* stdv, int64_t M, int L) {
     const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -89,11 +102,11 @@ __global__ __launch_bounds__(TPB) void features_states_kernel(const int32_t* sta
     Counts k;
     for (int h = 0; h < 2; ++h) {
         int n = 0;
-        for (int j = 0; j < L; ++j) n += s[h * L + j] != 0;
+        for (int j = 0; j < L; ++j) n += (int8_t)s[h * L + j] != 0;
         k.n[h] = n;
         k.c[h][0] = k.c[h][1] = k.c[h][2] = k.c[h][3] = 0;
         for (int j = 0; j < n; ++j) {
-            const int32_t v = s[h * L + j];
+            const int8_t v = (int8_t)s[h * L + j];
             k.c[h][0] += v == 1;
             k.c[h][1] += v == -1;
             k.c[h][2] += v == 2;

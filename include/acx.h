@@ -633,9 +633,15 @@ int64_t acx_sbfs_node_keys(void* h, uint64_t* keys, int64_t* gids, int64_t cap, 
  * or `keys` ((M, acx_key_words(L)) packed keys, e.g. acx_expand12 output) is non-NULL.
  *   acx_features   out (M,14) float32 = compute_features (feature_extraction.py:11-91); with
  *                  mean/std (14 float32 each, both or neither) normalised (f - mean) / std as
- *                  _score_states_mlp does (value_guided_search.py:49-66).
+ *                  _score_states_mlp does (value_guided_search.py:49-66): one IEEE float32
+ *                  subtract and divide (denormal quotients kept, overflow to +-inf).  The two
+ *                  ratios are the correctly rounded float32 quotients of the lengths.  `states`
+ *                  may hold any int32 letters: each is truncated to int8 first, as the reference
+ *                  does (257 counts as x, 256 as padding), and a relator's letters are its first
+ *                  count_nonzero entries.
  *   acx_token_ids  out (M, max_state_dim) int64 = letter + 2, padded with 2
- *                  (_score_states_seq, value_guided_search.py:68-84); max_state_dim >= 2L.
+ *                  (_score_states_seq, value_guided_search.py:68-84); max_state_dim >= 2L.  The
+ *                  int32 letter is widened as it is, without the int8 truncation.
  */
 int acx_features(const int32_t* states, const uint64_t* keys, const float* mean, const float* stdv, float* out,
                  int64_t M, int32_t L, void* stream);

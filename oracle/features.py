@@ -7,7 +7,9 @@ compute_features  restates value_search/feature_extraction.py:11-91 (14 features
 normalise         (f - mean) / std in float32, value_guided_search.py:58-59.
 token_ids         value_guided_search.py:68-84: letter + 2 as int64, padded with 2.
 Pinned by tests/test_oracle.py against tests/golden/features.npz (made by running the
-reference's own compute_features, tests/golden/make_golden.py --features)."""
+reference's own compute_features, tests/golden/make_golden.py --features) and, for int32 rows
+outside the packed domain (compute_features casts to int8, token_ids does not), against
+tests/golden/features_edges.npz (--features-edges)."""
 
 from __future__ import annotations
 

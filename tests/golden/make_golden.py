@@ -548,6 +548,75 @@ def gen_features(root, ms, rng):
     return out
 
 
+# int32 letters that np.int8 maps to 0, +-1 and +-2 (value mod 256), and their plain forms
+EDGE_MOD256 = [256, 257, 258, 254, 255, -255, -256, -254, -257, -258, 65536, 65537, -65535, 2 ** 31 - 1, 2 ** 31 - 2,
+               -2 ** 31, -2 ** 31 + 1, -2 ** 31 + 2, 2 ** 31 - 256, 2 ** 31 - 255]
+EDGE_LS = (4, 19, 64)
+
+
+def features_edge_rows(L, rng, n_random=300):
+    """(n, 2L) int32 rows outside what features.npz holds: empty relators, zeros inside a relator,
+    letters beyond +-2, letters that are 0, +-1, +-2 only mod 256, and random mixtures of them"""
+    rows = []
+
+    def row(r0, r1):
+        s = np.zeros(2 * L, np.int64)
+        s[:len(r0)], s[L:L + len(r1)] = r0, r1
+        rows.append(s)
+
+    gens = [1, -1, 2, -2]
+    full = [gens[i % 4] for i in range(L)]
+    row([], [])                                     # both relators empty
+    for w in ([1], full[:L // 2], full):            # each one empty
+        row(w, [])
+        row([], w)
+    for w in (full, full[:3]):                      # a zero at the front and in the middle of a relator
+        for at in (0, 1, len(w) // 2, len(w) - 2):
+            z = list(w)
+            z[at] = 0
+            row(z, w)
+            row(w, z)
+            row(z, z)
+    row([0, 0, 1, 2][:L], [0, -1, 0, -2][:L])       # several zeros: the window is shorter than the letters' span
+    big = list(range(3, 128)) + list(range(-3, -129, -1))
+    for i in range(0, len(big), L):                 # letters 3 .. 127 and -3 .. -128, every one
+        w = big[i:i + L]
+        row(w, full[:1 + i % L])
+        row(full[:1 + (i // L) % L], w)
+        row([w[j] if j % 2 else gens[j % 4] for j in range(len(w))], w[::-1])
+    for i, v in enumerate(EDGE_MOD256):             # letters = 0, +-1, +-2 mod 256
+        row([v], [2])
+        row([1, v, -2, v][:L], [v, v, 1][:L])
+        row(full, [gens[j % 4] if j != i % L else v for j in range(L)])
+    row([257, 256, 1, 0][:L], [2])                  # (the row quoted with the fixture's test)
+    pool = np.array(gens * 6 + [0] * 3 + [3, -3, 5, 100, 127, -128, -100] + EDGE_MOD256, np.int64)
+    for _ in range(n_random):
+        s = np.zeros(2 * L, np.int64)
+        for h in range(2):
+            n = int(rng.integers(0, L + 1))
+            s[h * L:h * L + n] = rng.choice(pool, n)
+        rows.append(s)
+    st = np.stack(rows)
+    assert st.min() >= -2 ** 31 and st.max() < 2 ** 31
+    return st.astype(np.int32)
+
+
+def gen_features_edges(root):
+    """tests/golden/features_edges.npz: the reference's own compute_features on features_edge_rows"""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("ref_feature_extraction",
+                                                  os.path.join(root, "value_search", "feature_extraction.py"))
+    fe = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fe)
+    out = {}
+    for L in EDGE_LS:
+        st = features_edge_rows(L, np.random.default_rng(1900 + L))
+        out[f"L{L}_states"] = st
+        out[f"L{L}_features"] = np.stack([fe.compute_features(x, L) for x in st]).astype(np.float32)
+    return out
+
+
 def gen_kat_paths(ref, root, ms):
     """Known-answer action sequences: the 17 exact replays of
     tests/test_solution_verification.py:503-577, the notebook AC paths, Stable-AK3."""
@@ -656,6 +725,11 @@ if __name__ == "__main__":
         ms = np.load(os.path.join(PKG_DATA, "all_presentations.npy"))
         np.savez_compressed(os.path.join(HERE, "features.npz"),
                             **gen_features(root, ms, np.random.default_rng(11)))
+    elif "--features-edges" in sys.argv:  # only (re)generate features_edges.npz
+        sys.argv.remove("--features-edges")
+        ap = argparse.ArgumentParser()
+        ap.add_argument("--reference", required=True, help="a checkout of the reference project")
+        np.savez_compressed(os.path.join(HERE, "features_edges.npz"), **gen_features_edges(ap.parse_args().reference))
     elif "--unit" in sys.argv:  # only (re)generate unit_cases.json
         sys.argv.remove("--unit")
         ap = argparse.ArgumentParser()

@@ -2,6 +2,8 @@
 417-561) for the batched beam search (acx.beam_search_many, acx.beam_search).
 
     python tests/golden/make_golden_beam.py --reference ROOT [--procs N]
+    python tests/golden/make_golden_beam.py --reference ROOT --scored    (beam_search_scored.json,
+        real-valued scores: scored_cases() below; beam_search.json is left as it is)
 
 The reference is loaded as make_golden.py loads it: bare package modules for ac_solver,
 ac_solver.envs and value_search, so the learner's imports are never run.  Every run is the
@@ -66,9 +68,13 @@ def run_case(args):
     root, case = args
     import torch
     torch.set_num_threads(1)
-    from beam_yardstick import SCORERS
+    from beam_yardstick import NORM_MEAN, NORM_STD, SCORERS, TOKEN_SCORERS
     beam_search = load_beam_search(root)
-    fn = SCORERS[case["scorer"]][1]
+    arch = case.get("arch", "mlp")
+    fn = (SCORERS if arch == "mlp" else TOKEN_SCORERS)[case["scorer"]][1]
+    mean, std = (NORM_MEAN, NORM_STD) if case.get("norm") else (np.zeros(14, np.float32), np.ones(14, np.float32))
+    if arch != "mlp":
+        mean = std = None
     seen = set()
 
     class Model(torch.nn.Module):
@@ -80,7 +86,7 @@ def run_case(args):
     pres = np.array(case["presentation"], np.int8)
     rec = dict(case)
     try:
-        ok, path, st = beam_search(pres, Model(), "mlp", np.zeros(14, np.float32), np.ones(14, np.float32),
+        ok, path, st = beam_search(pres, Model(), arch, mean, std,
                                    beam_width=case["W"], max_nodes_to_explore=case["budget"], device="cpu",
                                    cyclically_reduce_after_moves=case["cyclical"])
         rec.update(raises=False, ok=bool(ok), path=to_jsonable(path), nodes_explored=int(st["nodes_explored"]),
@@ -151,6 +157,38 @@ def all_cases():
     return cases
 
 
+SCORED_W = (3, 50, 86, 342)  # 50 | 86 | 342: one width per LDS class of the select kernel
+
+
+def scored_cases():
+    """beam_search_scored.json: real-valued scores.  'mlp' with beam_yardstick's NORM_MEAN / NORM_STD
+    passed to the reference and a scorer of NORM_SCORERS on the normalised features; 'seq' with the
+    token scorer TOK.  AK(2) at L = 7, AK(3) at L = 18, twelve Miller-Schupp rows at L = 36; W in
+    SCORED_W, budgets <= 3,000 (<= 7,000 at W = 342), both flags."""
+    from beam_yardstick import NORM_SCORERS
+    scorers = [("mlp", s) for s in NORM_SCORERS] + [("seq", "TOK")]
+
+    def scored(name, p, arch, s, W, budget, cyc):
+        c = case(name, p, s, W, budget, cyc)
+        c.update(arch=arch, norm=arch == "mlp")
+        return c
+
+    cases, i = [], 0
+    for name, p in (("AK2", AK2), ("AK3", AK3)):
+        for arch, s in scorers:
+            for W in SCORED_W[:3]:
+                cases.append(scored(f"ak-{name}", p, arch, s, W, 3000 - 7 * i, bool(i % 2)))
+                i += 1
+    for j, (arch, s) in enumerate(scorers):
+        cases.append(scored("ak-AK3", AK3, arch, s, 342, 7000 - 11 * j, bool(j % 2)))
+    ms = np.load(os.path.join(PKG_DATA, "all_presentations.npy"))
+    for j, r in enumerate(ms[17:: len(ms) // 12][:12]):
+        arch, s = scorers[j % len(scorers)]
+        cases.append(scored("ms", repad(r, MS_L), arch, s, SCORED_W[(j // 2) % 3], 3000 - 100 * j, bool(j % 4 >= 2)))
+    cases.append(scored("ms", repad(ms[-1], MS_L), "mlp", "NNEG", 342, 7000, False))
+    return cases
+
+
 def check_not_vacuous(recs):
     kinds = {}
     for r in recs:
@@ -169,10 +207,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", required=True, help="a checkout of the reference project")
     ap.add_argument("--procs", type=int, default=min(16, os.cpu_count() or 1))
+    ap.add_argument("--scored", action="store_true", help="write beam_search_scored.json only")
     args = ap.parse_args()
-    cases = all_cases()
+    cases = scored_cases() if args.scored else all_cases()
     with Pool(args.procs) as pool:
         recs = pool.map(run_case, [(args.reference, c) for c in cases], chunksize=1)
+    if args.scored:
+        assert not any(r["raises"] for r in recs)
+        ends = {"found" if r["ok"] else "budget" if r["nodes_explored"] >= r["budget"] else "died" for r in recs}
+        assert ends == {"found", "budget", "died"}, ends
+        with open(os.path.join(HERE, "beam_search_scored.json"), "w") as f:
+            json.dump(recs, f, separators=(",", ":"))
+        print(len(recs), "records", sorted(ends))
+        return
     kinds = check_not_vacuous(recs)
     with open(os.path.join(HERE, "beam_search.json"), "w") as f:
         json.dump(recs, f, separators=(",", ":"))

@@ -90,6 +90,105 @@ def test_scorers_agree_between_numpy_and_torch():
         assert a.tobytes() == b.tobytes(), name  # bit for bit: S4's zeros keep their signs
 
 
+# ---------------------------------------------------------------------------------------------
+# real-valued, normalised scores: tests/golden/beam_search_scored.json (make_golden_beam.py --scored)
+# ---------------------------------------------------------------------------------------------
+def _norm_of(c):
+    return dict(mean=Y.NORM_MEAN, std=Y.NORM_STD) if c["norm"] else {}
+
+
+@pytest.fixture(scope="module")
+def scored_runs():
+    """(record, the yardstick's run of it) for every record of the scored fixture"""
+    return [(c, Y.beam(np.array(c["presentation"]), c["scorer"], c["W"], c["budget"], c["cyclical"], **_norm_of(c)))
+            for c in _load("beam_search_scored.json")]
+
+
+@pytest.fixture(scope="module")
+def table_runs():
+    return [(W, Y.beam(p, "TABLE", W, budget, cyc)) for p, W, budget, cyc in Y.table_cases()]
+
+
+def test_the_scored_fixture_covers_what_it_is_for(scored_runs):
+    recs = [c for c, _ in scored_runs]
+    assert {c["L"] for c in recs} == {7, 18, 36} and sum(c["L"] == 36 for c in recs) >= 12
+    assert {(c["arch"], c["scorer"]) for c in recs} == {("mlp", s) for s in Y.NORM_SCORERS} | {("seq", "TOK")}
+    assert all(c["norm"] == (c["arch"] == "mlp") for c in recs) and not any(c["raises"] for c in recs)
+    assert {c["W"] for c in recs} == {3, 50, 86, 342} and {c["cyclical"] for c in recs} == {False, True}
+    assert all(c["budget"] <= (7000 if c["W"] == 342 else 3000) for c in recs)
+    assert {_end(c) for c in recs} == {"found", "budget", "died"}
+    assert len(set(Y.NORM_MEAN.tolist())) == 14 and len(set(Y.NORM_STD.tolist())) == 14 and (Y.NORM_STD < 0).any()
+    # the integer columns: an integer mean and a power-of-two std (their normalised values are dyadic)
+    assert (Y.NORM_MEAN[:12] == np.round(Y.NORM_MEAN[:12])).all() and (np.frexp(Y.NORM_STD[:12])[0] == np.sign(
+        Y.NORM_STD[:12]) * 0.5).all()
+
+
+def test_yardstick_reproduces_every_scored_reference_record(scored_runs):
+    """the reference's beam_search with the non-trivial mean / std ('mlp') and on token ids ('seq')"""
+    for c, y in scored_runs:
+        assert not y["raises"], c
+        assert (y["ok"], y["path"], y["nodes"], y["steps"]) == (c["ok"], c["path"], c["nodes_explored"], c["steps"]), c
+        assert y["status"] == {"found": Y.FOUND, "budget": Y.BUDGET, "died": Y.EXHAUSTED}[_end(c)], c
+
+
+def test_the_scored_searches_are_not_vacuous(scored_runs, table_runs):
+    """by the yardstick's report: in every (scorer, W) group a step selected from more candidates than
+    W and some step tied across the W boundary; negative and non-integer scores occurred; the table
+    scorer returned every entry of its table, and a step held both zeros"""
+    groups = {}
+    for c, y in scored_runs:
+        groups.setdefault((c["scorer"], c["W"]), []).append(y)
+    for W, y in table_runs:
+        groups.setdefault(("TABLE", W), []).append(y)
+    assert set(groups) == {(s, W) for s in list(Y.NORM_SCORERS) + ["TOK"] for W in (3, 50, 86, 342)} | {
+        ("TABLE", W) for W in (50, 86, 342)}
+    for (s, W), ys in groups.items():
+        assert any(max(y["cands"], default=0) > W for y in ys), (s, W)
+    assert sum(bool(y["tie_steps"]) for _, y in scored_runs) >= 10
+    for s in list(Y.NORM_SCORERS) + ["TOK", "TABLE"]:
+        assert any(y["tie_steps"] for (s2, _), ys in groups.items() if s2 == s for y in ys), s
+    for s in Y.NORM_SCORERS:
+        v = np.array(sorted(set().union(*(y["score_bits"] for (s2, _), ys in groups.items() if s2 == s for y in ys))),
+                     np.uint32).view(np.float32)
+        assert len(v) >= 20 and (v != np.round(v)).any(), (s, v)
+        # N12 lies in [2, 4], so NMAX is >= 2, and N13 is max / min - 1 >= 0: NNEG brings the negatives
+        assert (v < 0).any() == (s == "NNEG") and (s != "NNEG" or (v > 0).any()), (s, v)
+    for W, y in table_runs:
+        assert y["score_bits"] == set(Y.TABLE_BITS.tolist()) and y["zero_steps"] and y["tie_steps"], W
+        assert y["steps"] >= 5
+
+
+def test_a_skipped_normalisation_changes_the_negative_std_search(scored_runs):
+    """NNEG's column 2 has a negative std: without mean / std the same scorer orders the candidates
+    differently, and the recorded searches end differently -- so a beam search that dropped the
+    normalisation cannot reproduce these records"""
+    recs = [(c, y) for c, y in scored_runs if c["scorer"] == "NNEG" and c["L"] >= 18]
+    assert len(recs) >= 5
+    for c, y in recs:
+        raw = Y.beam(np.array(c["presentation"]), "NNEG", c["W"], c["budget"], c["cyclical"])
+        assert (raw["ok"], raw["path"], raw["nodes"], raw["steps"]) != (y["ok"], y["path"], y["nodes"], y["steps"]), c
+
+
+def test_real_valued_scorers_agree_between_numpy_and_torch(scored_runs, table_runs):
+    """bit for bit, on the states the searches visited: the normalised features' scorers, the token
+    scorer and the table (whose zeros, denormals and infinities keep their bits)"""
+    for L in (18, 36):
+        st = np.concatenate([np.stack(y["states"]) for c, y in scored_runs if c["L"] == L and c["W"] == 50])[:4000]
+        f = Y.normalise_np(Y.features_np(st, L), Y.NORM_MEAN, Y.NORM_STD)
+        for name, (fn, ft) in Y.NORM_SCORERS.items():
+            a, b = np.asarray(fn(f), np.float32), ft(torch.from_numpy(f)).to(torch.float32).numpy()
+            assert a.tobytes() == b.tobytes() and len(np.unique(a)) >= 10, name
+        t = st.astype(np.int64) + 2
+        for name, (fn, ft) in Y.TOKEN_SCORERS.items():
+            a, b = np.asarray(fn(t)), ft(torch.from_numpy(t)).numpy()
+            assert a.dtype == b.dtype == np.float32 and a.tobytes() == b.tobytes(), name
+        assert set(Y._table_np(t).view(np.uint32).tolist()) == set(Y.TABLE_BITS.tolist())
+    v = Y.TABLE
+    assert np.isinf(v).sum() == 2 and (v == 0).sum() == 2 and np.float32(1).view(np.uint32) + 1 in Y.TABLE_BITS
+    assert np.nextafter(np.float32(-1), np.float32(0)) in v and np.nextafter(np.float32(-1), np.float32(-2)) in v
+    assert np.finfo(np.float32).max in v and -np.finfo(np.float32).max in v and len(np.unique(v)) < len(v) - 4
+
+
 def _build(tmp, flags, name):
     exe = str(tmp / name)
     subprocess.check_call(["g++", "-std=c++17", *flags, "-I", os.path.join(REPO, "include"), "-I",

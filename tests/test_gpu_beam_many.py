@@ -4,7 +4,9 @@ float32 values are exact, every search gives the reference's beam_search result
 (value_search/value_guided_search.py:417-561) -- against the reference's recorded runs
 (tests/golden/beam_search.json) and against the yardstick tests/beam_yardstick.py (checked on the
 CPU by test_beam_cpu.py).  A call has one scorer, so the fixture's records are grouped by
-(L, flag, scorer)."""
+(L, flag, scorer).  The scoring path itself -- normalised features, token ids, scores over the
+whole float line, what a scorer may return -- is tested with real-valued scorers against
+tests/golden/beam_search_scored.json and the yardstick."""
 import functools
 
 import numpy as np
@@ -241,6 +243,197 @@ def test_nan_scorer_raises_and_leaves_the_handle_usable():
         acx.beam_search_many(pres, nan, beam_width=50, max_nodes_to_explore=3000, device=DEV)
     assert calls and B._HANDLES == h
     assert _same(_many(pres, "S1", 50, 3000), want) and want[0][0][0] and want[0][1][0]
+
+
+# ---------------------------------------------------------------------------------------------
+# real-valued scores: normalised features, token ids, the float line (beam_search_scored.json)
+# ---------------------------------------------------------------------------------------------
+def _scored_kw(c):
+    """how a scored record's scorer reaches beam_search_many: (the torch form, its keyword arguments)"""
+    if c["arch"] == "mlp":
+        return Y.SCORERS[c["scorer"]][1], dict(feat_mean=Y.NORM_MEAN, feat_std=Y.NORM_STD) if c["norm"] else {}
+    return Y.TOKEN_SCORERS[c["scorer"]][1], dict(scorer_input="tokens")
+
+
+def test_every_scored_record_grouped_into_single_calls():
+    """the reference's beam_search with a non-trivial mean / std ('mlp': scores from normalised
+    columns, the two ratio columns among them) and on token ids ('seq'), grouped by (L, flag, scorer,
+    mean / std): ops.features(keys=, mean=, std=) is the only source of these scores"""
+    groups = {}
+    for c in _load("beam_search_scored.json"):
+        groups.setdefault((c["L"], c["cyclical"], c["arch"], c["scorer"], c["norm"]), []).append(c)
+    assert sum(len(g) for g in groups.values()) >= 45 and {k[0] for k in groups} == {7, 18, 36}
+    for (L, cyc, arch, scorer, norm), recs in sorted(groups.items()):
+        fn, kw = _scored_kw(recs[0])
+        res, st = _many(np.array([c["presentation"] for c in recs]), fn, [c["W"] for c in recs],
+                        [c["budget"] for c in recs], cyc, **kw)
+        for i, c in enumerate(recs):
+            _check_record(res, st, i, c)
+
+
+class _FnModel(torch.nn.Module):
+    def __init__(self, fn):
+        super().__init__()
+        self.fn = fn
+
+    def forward(self, x):
+        return self.fn(x)[:, None]
+
+
+@pytest.mark.parametrize("arch", ["mlp", "seq"])
+def test_scored_records_through_beam_search(arch):
+    """the reference's signature: 'mlp' with the real mean / std, and the token branch
+    (architecture != 'mlp').  expm1 is strictly increasing over every value these scorers returned
+    in the reference's runs (make_golden_beam.py asserts it), and distinct values lie a relative
+    1e-4 or more apart (quotients of lengths up to 36, eighths, integers), a thousand float32
+    roundings: an expm1 that is a few ulps off orders them the same."""
+    import acx
+    recs = [c for c in _load("beam_search_scored.json") if c["arch"] == arch]
+    assert len(recs) >= 9 and {c["W"] for c in recs} == {3, 50, 86, 342}
+    for c in recs:
+        fn, _ = _scored_kw(c)
+        mean, std = (Y.NORM_MEAN, Y.NORM_STD) if arch == "mlp" else (None, None)
+        ok, path, stats = acx.beam_search(np.array(c["presentation"], np.int8), _FnModel(fn).to(DEV), arch, mean, std,
+                                          beam_width=c["W"], max_nodes_to_explore=c["budget"], device=DEV,
+                                          cyclically_reduce_after_moves=c["cyclical"])
+        assert (ok, [list(x) for x in path], stats) == (c["ok"], c["path"], dict(nodes_explored=c["nodes_explored"],
+                                                                                 steps=c["steps"])), c
+
+
+def test_without_its_normalisation_the_negative_std_search_differs():
+    """the NNEG records rerun WITHOUT mean / std: the GPU gives the yardstick's un-normalised search,
+    which is not the recorded one -- so the records above cannot pass if the normalisation is skipped"""
+    recs = [c for c in _load("beam_search_scored.json") if c["scorer"] == "NNEG" and c["L"] == 18 and not c["cyclical"]]
+    assert len(recs) >= 2
+    res, st = _many(np.array([c["presentation"] for c in recs]), "NNEG", [c["W"] for c in recs],
+                    [c["budget"] for c in recs])
+    for i, c in enumerate(recs):
+        raw = Y.beam(np.array(c["presentation"]), "NNEG", c["W"], c["budget"])
+        _check_yardstick(res, st, i, raw, c)
+        assert (raw["ok"], raw["path"], raw["nodes"], raw["steps"]) != (c["ok"], c["path"], c["nodes_explored"], c["steps"])
+
+
+@pytest.mark.parametrize("case", range(3))
+def test_table_scorer_over_the_float_line_against_yardstick(case):
+    """beam_select_kernel on +-inf, +-0.0, +-the smallest denormal, +-FLT_MAX, 1.0 and -1.0 with both
+    their neighbours and planted duplicates, at W = 50, 86 and 342: one per LDS class.  (That every
+    entry is returned, that a step holds both zeros and that steps tie across W: test_beam_cpu.py.)"""
+    p, W, budget, cyc = Y.table_cases()[case]
+    seen = []
+
+    def table(t):
+        seen.append(t.cpu().numpy())
+        return Y.TOKEN_SCORERS["TABLE"][1](t)
+
+    res, st = _many(p[None], table, W, budget, cyc, scorer_input="tokens")
+    y = Y.beam(p, "TABLE", W, budget, cyc)
+    _check_yardstick(res, st, 0, y, (W, budget))
+    assert y["steps"] >= 5 and max(y["cands"]) > W and y["zero_steps"] and y["tie_steps"]
+    # These searches find nothing, and their endings say little about the order of the scores.  The
+    # candidates of a step do: they are the children of the beam selected the step before, so every
+    # step's scorer input equals the yardstick's new nodes of that step exactly when every
+    # selection was the stable sort's.
+    nodes = np.stack(y["states"]).astype(np.int64) + 2
+    bounds = [1] + y["nodes_after"]
+    assert len(seen) == sum(c > 0 for c in y["cands"])  # (a step without candidates is not scored)
+    for i, t in enumerate(seen):
+        assert np.array_equal(t, nodes[bounds[i]:bounds[i + 1]]), (W, "step", i + 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# the scorer contract (_batch_beam._scores) on a cached handle
+# ---------------------------------------------------------------------------------------------
+def _contract_batches():
+    """(the batch the odd scorers run on, another batch for the handle's next call): same L, the
+    second no larger in any dimension, so that the cached handle serves it"""
+    pres, budgets = _solvable()
+    return (pres[:12], budgets[:12]), (pres[20:30][::-1].copy(), budgets[20:30][::-1])
+
+
+@pytest.fixture(scope="module")
+def contract():
+    """the float32 results of both batches, each from a fresh handle"""
+    from acx.search import _batch_beam as B
+    first, second = _contract_batches()
+    B.release_workspaces()
+    want = _many(first[0], "S1", 7, first[1])
+    B.release_workspaces()
+    fresh = _many(second[0], "S1", 7, second[1])
+    B.release_workspaces()
+    assert any(r[0] for r in want[0]) and any(r[0] for r in fresh[0]) and want[1]["steps"].max() >= 4
+    return want, fresh
+
+
+def _with_cached_handle(run):
+    """run(first batch) on a handle a plain call has just cached; then the same handle must give a
+    fresh handle's results on the other batch"""
+    from acx.search import _batch_beam as B
+    first, second = _contract_batches()
+    B.release_workspaces()
+    _many(first[0], "S1", 7, first[1])
+    h = dict(B._HANDLES)
+    assert len(h) == 1
+    out = run(first)
+    assert B._HANDLES == h
+    after = _many(second[0], "S1", 7, second[1])
+    assert B._HANDLES == h
+    B.release_workspaces()
+    return out, after
+
+
+S1_T = Y.SCORERS["S1"][1]  # integers in [0, 80]: exact in float16 too
+
+
+@pytest.mark.parametrize("form", ["column", "float64", "float16", "float64 column"])
+def test_scorer_outputs_taken_as_float32(contract, form):
+    """(M, 1), float64 and float16 outputs of an integer-valued scorer give the float32 result"""
+    forms = {"column": lambda f: S1_T(f)[:, None], "float64": lambda f: S1_T(f).to(torch.float64),
+             "float16": lambda f: S1_T(f).to(torch.float16), "float64 column": lambda f: S1_T(f).to(torch.float64)[:, None]}
+    want, fresh = contract
+    out, after = _with_cached_handle(lambda b: _many(b[0], forms[form], 7, b[1]))
+    assert _same(out, want) and _same(after, fresh)
+
+
+@pytest.mark.parametrize("form", ["two columns", "one short", "scalar", "cpu", "numpy", "list", "none"])
+def test_scorer_outputs_refused(contract, form):
+    """a wrong shape, a CPU tensor and a non-tensor each raise ValueError, before anything is
+    selected; the handle stays usable"""
+    import acx
+    forms = {"two columns": lambda f: f[:, :2], "one short": lambda f: S1_T(f)[:-1], "scalar": lambda f: S1_T(f).sum(),
+             "cpu": lambda f: S1_T(f).cpu(), "numpy": lambda f: S1_T(f).cpu().numpy(),
+             "list": lambda f: S1_T(f).tolist(), "none": lambda f: None}
+    calls = []
+
+    def scorer(f):
+        calls.append(len(f))
+        return forms[form](f)
+
+    def run(b):
+        with pytest.raises(ValueError, match="the scorer must return"):
+            acx.beam_search_many(b[0], scorer, beam_width=7, max_nodes_to_explore=b[1], device=DEV)
+
+    _, after = _with_cached_handle(run)
+    assert len(calls) == 1 and calls[0] > 0 and _same(after, contract[1])
+
+
+def test_scorer_that_raises_mid_run_propagates(contract):
+    """a RuntimeError on the scorer's third call reaches the caller as it is; the searches it
+    abandoned between expand and select leave nothing behind for the handle's next run"""
+    import acx
+    calls = []
+
+    def scorer(f):
+        calls.append(len(f))
+        if len(calls) == 3:
+            raise RuntimeError("the model broke")
+        return S1_T(f)
+
+    def run(b):
+        with pytest.raises(RuntimeError, match="the model broke"):
+            acx.beam_search_many(b[0], scorer, beam_width=7, max_nodes_to_explore=b[1], device=DEV)
+
+    _, after = _with_cached_handle(run)
+    assert len(calls) == 3 and _same(after, contract[1])
 
 
 # ---------------------------------------------------------------------------------------------

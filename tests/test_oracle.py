@@ -152,3 +152,33 @@ def test_features_oracle_vs_reference_golden():
         assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), exp.view(np.uint32)), L
     tok = F.token_ids(d["L18_states"], 72)
     assert tok.dtype == np.int64 and (tok[:, 36:] == 2).all() and np.array_equal(tok[:, :36], d["L18_states"] + 2)
+
+
+def test_features_oracle_vs_reference_edge_golden():
+    """tests/golden/features_edges.npz (make_golden.py --features-edges): the reference's own
+    compute_features on int32 rows with empty relators, zeros inside a relator, letters beyond +-2
+    and letters that are 0, +-1, +-2 only after its int8 cast; and that the fixture holds them."""
+    from oracle import features as F
+    d = np.load(os.path.join(GOLDEN, "features_edges.npz"))
+    assert os.path.getsize(os.path.join(GOLDEN, "features_edges.npz")) < os.path.getsize(
+        os.path.join(GOLDEN, "features.npz")) // 2
+    for L in (4, 19, 64):
+        st, exp = d[f"L{L}_states"], d[f"L{L}_features"]
+        assert st.dtype == np.int32 and 300 <= len(st) <= 700
+        got = F.compute_features_batch(st, L)
+        assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), exp.view(np.uint32)), L
+        w = st.astype(np.int8)
+        wrapped = (st != w) & (np.abs(w) <= 2)  # letters that are 0, +-1, +-2 only mod 256
+        assert {int(x) for x in np.unique(w[wrapped])} == {-2, -1, 0, 1, 2}
+        assert {2 ** 31 - 1, -2 ** 31, 256, 257, -255} <= {int(x) for x in np.unique(st)}
+        assert set(range(3, 128)) | set(range(-128, -2)) <= {int(x) for x in np.unique(st)}
+        n = [(w[:, h * L:(h + 1) * L] != 0).sum(1) for h in range(2)]
+        assert ((n[0] == 0) & (n[1] == 0)).any() and ((n[0] == 0) & (n[1] > 0)).any() and ((n[0] > 0) & (n[1] == 0)).any()
+        assert (exp[(n[0] == 0) & (n[1] == 0)] == np.float32([0] * 12 + [0.5, 0])).all()
+        assert (w[:, 0] == 0).any() and ((w[:, 0] != 0) & (w[:, 1] == 0) & (w[:, 2] != 0)).any()  # zeros inside
+    # the row of the int8 finding: 257 is x and 256 is padding, so len_r1 = 2 and total = 3
+    row = np.array([257, 256, 1, 0, 2, 0, 0, 0], np.int32)
+    i = int(np.nonzero((d["L4_states"] == row).all(1))[0][0])
+    assert d["L4_features"][i].tolist()[:4] == [3.0, 2.0, 1.0, 1.0]
+    tok = F.token_ids(row[None], 9)  # token ids keep the letter: no int8 cast (_score_states_seq)
+    assert tok.tolist() == [[259, 258, 3, 2, 4, 2, 2, 2, 2]]
