@@ -139,6 +139,20 @@ SIGNATURES.update({
     "acx_beam_destroy": ([_P], None),
 })
 
+# value-guided greedy scored by the caller (ac-solver-caltech_amd/csrc/acx_vgreedy.hip): a step is
+# pop, gather, the scorer, push; a NaN score ends a search with BEAM_NAN, as in the beam search
+SIGNATURES.update({
+    "acx_vgreedy_bytes": ([_I32, _I64], ctypes.c_int64),
+    "acx_vgreedy_create": ([_I32, _I64, _I64, _I32], ctypes.c_void_p),
+    "acx_vgreedy_begin": ([_P, _P, _P, _I64, _P], ctypes.c_int),
+    "acx_vgreedy_pop": ([_P, _P, _P], ctypes.c_int),
+    "acx_vgreedy_gather": ([_P, _P, _I64, _P], ctypes.c_int),
+    "acx_vgreedy_push": ([_P, _P, _I64, _P], ctypes.c_int),
+    "acx_vgreedy_finish": ([_P] * 7, ctypes.c_int),
+    "acx_vgreedy_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
+    "acx_vgreedy_destroy": ([_P], None),
+})
+
 _lib = None
 
 

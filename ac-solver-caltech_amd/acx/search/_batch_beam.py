@@ -35,16 +35,39 @@ def release_workspaces() -> None:
     _batch_bfs._release(_BEAM)
 
 
-def _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore, scorer_input, feat_mean, feat_std,
-                   on_error):
-    """(states, budgets, widths (N) int32, mean, std as float32 arrays or None) or ValueError; no
-    GPU call."""
-    states, budgets = _batch_bfs._validate(presentations, max_nodes_to_explore, on_error, "beam_search_many")
-    N = len(states)
+def _validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error, name):
+    """the first checks of every search scored by the caller (_batch_vgreedy.py too): (states,
+    budgets) or ValueError; no GPU call."""
+    states, budgets = _batch_bfs._validate(presentations, max_nodes_to_explore, on_error, name)
     if not callable(scorer):
         raise ValueError("scorer must be callable")
     if scorer_input not in ("features", "tokens"):
         raise ValueError(f"scorer_input must be 'features' or 'tokens', not {scorer_input!r}")
+    return states, budgets
+
+
+def _validate_norm(scorer_input, feat_mean, feat_std):
+    """their last checks: (mean, std) as float32 arrays or (None, None), or ValueError"""
+    if (feat_mean is None) != (feat_std is None):
+        raise ValueError("pass both feat_mean and feat_std, or neither")
+    mean = std = None
+    if feat_mean is not None:
+        if scorer_input != "features":
+            raise ValueError("feat_mean / feat_std go with scorer_input='features'")
+        mean, std = (np.ascontiguousarray(torch.as_tensor(x).detach().cpu().numpy(), dtype=np.float32)
+                     for x in (feat_mean, feat_std))
+        if mean.shape != (14,) or std.shape != (14,):
+            raise ValueError("feat_mean and feat_std hold 14 values each")
+    return mean, std
+
+
+def _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore, scorer_input, feat_mean, feat_std,
+                   on_error):
+    """(states, budgets, widths (N) int32, mean, std as float32 arrays or None) or ValueError; no
+    GPU call."""
+    states, budgets = _validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error,
+                                       "beam_search_many")
+    N = len(states)
     if np.ndim(beam_width) == 0:
         if isinstance(beam_width, (bool, np.bool_)) or not isinstance(beam_width, (int, np.integer)):
             raise ValueError("beam_width must be an integer or a sequence of integers")
@@ -56,16 +79,7 @@ def _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore, scor
         w = w.astype(np.int64)
     if N and (int(w.min()) < 1 or int(w.max()) > MAX_WIDTH):
         raise ValueError(f"beam_width must lie in [1, {MAX_WIDTH}]")
-    if (feat_mean is None) != (feat_std is None):
-        raise ValueError("pass both feat_mean and feat_std, or neither")
-    mean = std = None
-    if feat_mean is not None:
-        if scorer_input != "features":
-            raise ValueError("feat_mean / feat_std go with scorer_input='features'")
-        mean, std = (np.ascontiguousarray(torch.as_tensor(x).detach().cpu().numpy(), dtype=np.float32)
-                     for x in (feat_mean, feat_std))
-        if mean.shape != (14,) or std.shape != (14,):
-            raise ValueError("feat_mean and feat_std hold 14 values each")
+    mean, std = _validate_norm(scorer_input, feat_mean, feat_std)
     return states, budgets, w.astype(np.int32), mean, std
 
 

@@ -24,8 +24,8 @@ class _Engine:
     _destroy (and _run, or the beam search's step calls), its cached handles, and which searches
     return a path.  `extra` names the shape arguments its _bytes and _create take after
     max_nodes_each (beam: max_width); a cached handle whose extras are at least the wanted ones is
-    reused if `reuse(cached extras, wanted extras)` also agrees.  _batch_greedy.py and
-    _batch_beam.py run their searches through the same code."""
+    reused if `reuse(cached extras, wanted extras)` also agrees.  _batch_greedy.py,
+    _batch_beam.py and _batch_vgreedy.py run their searches through the same code."""
 
     def __init__(self, name, prefix, handles, path_statuses, no_path, extra=(), reuse=None):
         self.name, self.prefix, self.handles = name, prefix, handles
@@ -85,11 +85,12 @@ def _release(eng) -> None:
 
 
 def release_workspaces() -> None:
-    """Free the cached batch workspaces (the batched greedy and beam searches' too)."""
+    """Free the cached batch workspaces (the batched greedy, beam and value-guided greedy searches' too)."""
     _release(_BFS)
-    from . import _batch_beam, _batch_greedy
+    from . import _batch_beam, _batch_greedy, _batch_vgreedy
     _batch_greedy.release_workspaces()
     _batch_beam.release_workspaces()
+    _batch_vgreedy.release_workspaces()
 
 
 def _validate(presentations, max_nodes_to_explore, on_error, name="bfs_many"):

@@ -557,7 +557,7 @@ void acx_mgreedy_destroy(void* h);
  *   acx_beam_destroy frees the workspace.
  * All calls are asynchronous on `stream` and must use the same stream between begin and finish.
  */
-#define ACX_BEAM_NAN (-5) /* per-search status: the scorer returned NaN for one of its candidates */
+#define ACX_BEAM_NAN (-5) /* per-search status: the scorer returned NaN for one of its candidates (acx_vgreedy_* too) */
 #define ACX_BEAM_MAX_WIDTH 1024
 int64_t acx_beam_bytes(int32_t L, int64_t max_nodes_each, int32_t max_width);
 void* acx_beam_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t max_width, int32_t cyclical);
@@ -571,6 +571,67 @@ int acx_beam_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, in
 int acx_beam_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
                    void* stream);
 void acx_beam_destroy(void* h);
+
+/*
+ * Value-guided greedy search over a batch of presentations, scored by the caller
+ * (csrc/acx_vgreedy.hip): one wave owns one search -- node store, visited set and the frontier, a
+ * min-heap ordered by (score, path length, node index) -- on a private slice of the handle's
+ * workspace, and a step of all searches is acx_vgreedy_pop, acx_vgreedy_gather, the caller's scorer
+ * on the gathered keys (acx_features / acx_token_ids read them as they are), acx_vgreedy_push.
+ * Given equal scores -- and equal scores for equal states -- every search gives the result of
+ * value_guided_greedy_search on its own presentation, value_search/value_guided_search.py:253-414
+ * with solution_cache=None and time_limit=None.  The root is not scored.
+ *   acx_vgreedy_bytes   (value_guided_search.py:253-414) workspace bytes per search for budgets up
+ *                       to max_nodes_each = B at max_relator_length L, kw = acx_key_words(L):
+ *                         (8 kw + 20) (B + 11) + 64 ceil((B + 23) / 4) + 140
+ *                       (the rows, heap and visited set of acx_mgreedy_bytes -- the budget is tested
+ *                       once per pop, after up to 12 appends --, the search's state, its verdict
+ *                       record and its five results); ACX_E_ARG for L outside [1, ACX_MAX_L] or B
+ *                       outside [1, 2^24].
+ *   acx_vgreedy_create  (value_guided_search.py:253-414) allocates n_searches times that on the
+ *                       current device; NULL on bad arguments or when the workspace does not fit.
+ *   acx_vgreedy_begin   (value_guided_search.py:294-336) the roots of n <= n_searches searches:
+ *                       `states` DEVICE (n, 2L) int32, `budgets` DEVICE (n) int64 (a budget < 1
+ *                       behaves as 1: one pop is run).  A state outside the packed domain gets
+ *                       ACX_MBFS_DOMAIN, a budget above max_nodes_each ACX_MBFS_OVERFLOW; neither is
+ *                       searched.
+ *   acx_vgreedy_pop     (value_guided_search.py:339-383) one pop of every search that has not ended:
+ *                       the least heap entry's 12 children in action order, the raising and trivial
+ *                       tests, the visited set; the new nodes are the step's candidates.  `pair`
+ *                       DEVICE (2) int64 receives M, the candidates of all searches, and the number
+ *                       of searches that have not ended.  M == 0 with searches left is a step
+ *                       without a scorer call; no searches left ends the loop.
+ *   acx_vgreedy_gather  (value_guided_search.py:386-393) `keys` DEVICE (M, kw) uint64: the
+ *                       candidates' packed keys in (search, candidate) order.
+ *   acx_vgreedy_push    (value_guided_search.py:398-411) `scores` DEVICE (M) float32 in that order,
+ *                       lower is better (-0.0 ties with +0.0): the candidates enter the heap, then
+ *                       the budget test len(state_to_id) >= budget ends a search with
+ *                       ACX_BFS_BUDGET.  A NaN among a search's scores ends it with ACX_BEAM_NAN
+ *                       (the beam search's value, shared); nothing of it is pushed.
+ *                       M must be the value acx_vgreedy_pop wrote: a search whose candidates
+ *                       do not fit M ends with ACX_MBFS_OVERFLOW.
+ *   acx_vgreedy_finish  (value_guided_search.py:368,413) outputs DEVICE arrays of n: status (an
+ *                       ACX_BFS_* value -- ACX_BFS_EXHAUSTED: the heap ran empty -- or a negative
+ *                       refusal), nodes (len(state_to_id) at the ending event; on ACX_BFS_FOUND
+ *                       before the last pop's children), steps (pops), min_length (over the root and
+ *                       the children looked at), path_len.
+ *   acx_vgreedy_paths   (value_guided_search.py:87-97,366-367) for every search with ACX_BFS_FOUND
+ *                       the reference's path [(action, total), ..., (action, 2)] (no root entry) in
+ *                       CSR form at offsets[q], as acx_mbfs_paths writes its paths.
+ *   acx_vgreedy_destroy frees the workspace.
+ * All calls are asynchronous on `stream` and must use the same stream between begin and finish.
+ */
+int64_t acx_vgreedy_bytes(int32_t L, int64_t max_nodes_each);
+void* acx_vgreedy_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t cyclical);
+int acx_vgreedy_begin(void* h, const int32_t* states, const int64_t* budgets, int64_t n, void* stream);
+int acx_vgreedy_pop(void* h, int64_t* pair, void* stream);
+int acx_vgreedy_gather(void* h, uint64_t* keys, int64_t M, void* stream);
+int acx_vgreedy_push(void* h, const float* scores, int64_t M, void* stream);
+int acx_vgreedy_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, int32_t* min_length,
+                       int64_t* path_len, void* stream);
+int acx_vgreedy_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
+                      void* stream);
+void acx_vgreedy_destroy(void* h);
 
 /*
  * Breadth-first search with the node store and the visited set partitioned over G GPUs by key

@@ -2,7 +2,7 @@
 budget 10^4, not cyclical -- what the reference's trivialize_miller_schupp_through_search (and, for
 greedy, scripts/parallel_search.py) does, one search per presentation.
 
-    python tools/bench_search_many.py --engine bfs|greedy|beam [--budget N] [--rows N] [--out PATH]
+    python tools/bench_search_many.py --engine bfs|greedy|beam|vgreedy [--budget N] [--rows N] [--out PATH]
 
 Once as a loop of acx.bfs / acx.greedy_search with engine="device" (one search per call,
 csrc/acx_bfs.hip / csrc/acx_greedy.hip) and once as one acx.bfs_many / acx.greedy_search_many call
@@ -22,7 +22,17 @@ API -- ops.expand12 once per step over every live beam, the children copied to t
 visited sets, the budget cut and the stable selection in Python -- on every fifth row (238), run
 once after a warm-up on 8 rows; its wall time is scaled by rows / 238 to set it beside the batch
 call, and the JSON says so.  The results of those 238 rows must be equal.  Writes
-profiles/beam_many/bench_beam_many.json."""
+profiles/beam_many/bench_beam_many.json.
+
+--engine vgreedy: the same rows through one acx.value_guided_greedy_search_many call
+(csrc/acx_vgreedy.hip), scorer S0 = the total length, timed the same way, with the split of a step
+into pop, gather + features (the host's read of the candidate count falls in it, or, at a step
+without candidates, in the time between steps), scorer and push from HIP events of a further run.
+Beside it the same search written with the parent commit's public API -- ops.expand12 once per pop
+step over every live search's popped node, the children copied to the host, the heaps (heapq) and the
+visited sets in Python -- on every fifth row (238), run once after a warm-up on 8 rows and scaled as
+for the beam.  The results of those 238 rows must be equal.  Writes
+profiles/vgreedy_many/bench_vgreedy_many.json."""
 import argparse
 import contextlib
 import io
@@ -51,7 +61,7 @@ ENGINES = {
 }
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--engine", choices=sorted(ENGINES) + ["beam"], required=True)
+ap.add_argument("--engine", choices=sorted(ENGINES) + ["beam", "vgreedy"], required=True)
 ap.add_argument("--width", type=int, default=50, help="beam width (--engine beam)")
 ap.add_argument("--budget", type=int, default=10 ** 4)
 ap.add_argument("--rows", type=int, default=0, help="only the first N presentations (0: all)")
@@ -223,6 +233,121 @@ def bench_beam():
     }
 
 
+class PhaseMarks:
+    """HIP events at the marks of _batch_vgreedy._run_group: each mark names the phase that has just
+    ended ("between": the host's time from the end of a step to the next pop's launch)"""
+
+    def __init__(self):
+        self.ev = []
+
+    def mark(self, phase):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        self.ev.append((phase, e))
+
+    def split(self):
+        torch.cuda.synchronize()
+        ms, steps = {}, 0
+        for (_, a), (phase, b) in zip(self.ev, self.ev[1:]):
+            ms[phase] = ms.get(phase, 0.0) + a.elapsed_time(b)
+            steps += phase == "pop"
+        return {"steps": steps, **{f"{n}_ms": v for n, v in sorted(ms.items())}}
+
+
+def host_vgreedy(rows, budget):
+    """value_guided_greedy_search of every row, scored by total length, with ops.expand12 as the only
+    device call (one per pop step, over the popped node of every live search): [(ok, path)], nodes,
+    min_length"""
+    import heapq
+    n = len(rows)
+    heaps = [[(0.0, 0, 0, r.tobytes())] for r in rows]
+    ids = [{r.tobytes(): 0} for r in rows]
+    parent = [{0: None} for _ in rows]
+    min_len = [int(np.count_nonzero(r)) for r in rows]
+    res, live = [(False, [])] * n, list(range(n))
+    while live:
+        pops = [heapq.heappop(heaps[q]) for q in live]
+        par = torch.from_numpy(np.stack([np.frombuffer(p[3], np.int32) for p in pops])).to(dev)
+        out = acx.ops.expand12(par, cyclical=False)
+        ch, lens, err = (out[k].cpu().numpy() for k in ("children", "lengths", "err"))
+        tot = lens.sum(2)
+        nxt = []
+        for j, q in enumerate(live):
+            _, plen, cur, _ = pops[j]
+            new, done = [], False
+            for a in range(12):
+                assert not err[j, a]
+                t = int(tot[j, a])
+                min_len[q] = min(min_len[q], t)
+                if t == 2:
+                    path, v = [(a, 2)], cur
+                    while parent[q][v] is not None:
+                        path.append(parent[q][v][:2])
+                        v = parent[q][v][2]
+                    res[q], done = (True, path[::-1]), True
+                    break
+                key = ch[j, a].astype(np.int32).tobytes()
+                if key not in ids[q]:
+                    new.append((key, a, t))
+            if done:
+                continue
+            for key, a, t in new:  # (twins: both pushed, as the reference does)
+                nid = len(parent[q])
+                parent[q][nid] = (a, t, cur)
+                ids[q][key] = nid
+                heapq.heappush(heaps[q], (float(t), plen + 1, nid, key))
+            if len(ids[q]) < budget and heaps[q]:
+                nxt.append(q)
+        live = nxt
+    return res, [len(d) for d in ids], min_len
+
+
+def bench_vgreedy():
+    from acx.search import _batch_vgreedy
+
+    def many(r=rows):
+        return acx.value_guided_greedy_search_many(r, s0, max_nodes_to_explore=args.budget, device=dev,
+                                                   return_stats=True)
+
+    (batch_res, stats), batch_walls = timed(many, "batch")
+    marks = PhaseMarks()
+    _batch_vgreedy._TIMING = marks
+    try:
+        many()
+    finally:
+        _batch_vgreedy._TIMING = None
+    sub = rows[::5]
+    host_vgreedy(sub[:8], args.budget)  # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    host_res, host_nodes, host_min = host_vgreedy(sub, args.budget)
+    host_wall = time.perf_counter() - t0
+    print(f"host: {host_wall * 1e3:.2f} ms for {len(sub)} rows", file=sys.stderr, flush=True)
+    assert norm(host_res) == norm(batch_res[::5]), "value_guided_greedy_search_many and the host-side search disagree"
+    assert np.array_equal(stats["nodes"][::5], np.array(host_nodes))
+    assert np.array_equal(stats["min_length"][::5], np.array(host_min))
+    h = _batch_vgreedy._HANDLES[(0, L, False)]
+    return {
+        "workload": f"value_guided_greedy_search of {N} Miller-Schupp presentations, L = {L}, budget {args.budget}, "
+                    "scorer S0 (total length), not cyclical",
+        "device": torch.cuda.get_device_name(dev),
+        "searches": N, "solved": int(sum(bool(r[0]) for r in batch_res)),
+        "left_on_budget": int((stats["status"] == _lib.BFS_BUDGET).sum()),
+        "heap_ran_empty": int((stats["status"] == _lib.BFS_EXHAUSTED).sum()),
+        "nodes_total": int(stats["nodes"].sum()), "pops_total": int(stats["steps"].sum()),
+        "pops_max": int(stats["steps"].max()),
+        "batch_wall_ms": min(batch_walls) * 1e3, "batch_walls_ms": [w * 1e3 for w in batch_walls],
+        "batch_step_split_hip_events": marks.split(),
+        "host_rows": len(sub), "host_wall_ms": host_wall * 1e3, "host_runs": 1,
+        "host_wall_scaled_to_all_rows_ms": host_wall * 1e3 * N / len(sub),
+        "host_scaled_note": f"the host-side search ran on every fifth row ({len(sub)}); its wall time is scaled by "
+                            f"{N}/{len(sub)} to stand beside the batch call",
+        "host_scaled_over_batch": host_wall * N / len(sub) / min(batch_walls),
+        "batch_workspace_bytes": int(h[1] * _lib.load().acx_vgreedy_bytes(L, h[2])),
+        "results_equal": True,
+    }
+
+
 def write(out):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
@@ -231,8 +356,8 @@ def write(out):
     print(json.dumps(out))
 
 
-if args.engine == "beam":
-    write(bench_beam())
+if args.engine in ("beam", "vgreedy"):
+    write(bench_beam() if args.engine == "beam" else bench_vgreedy())
     sys.exit(0)
 
 (loop_res, loop_nodes), loop_walls = timed(loop, "loop")
