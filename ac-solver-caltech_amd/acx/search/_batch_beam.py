@@ -10,15 +10,13 @@ the scorer's."""
 from __future__ import annotations
 
 import numpy as np
-import torch
 
-from .. import _lib, ops
-from . import _batch_bfs
+from .. import _lib
+from . import _batch_bfs, _scored
 
 _HANDLES = {}  # (device, L, cyclical) -> (handle, searches, max_nodes_each, max_width)
 MAX_WIDTH = _lib.BEAM_MAX_WIDTH
 NO_PATH = (False, [])
-_TIMING = None  # tools/bench_search_many.py: an object whose mark() is called between a step's phases
 
 
 def _wclass(w):
@@ -28,6 +26,10 @@ def _wclass(w):
 # (a wider handle selects in a larger LDS class: reused only within its class)
 _BEAM = _batch_bfs._Engine("beam_search_many", "acx_beam", _HANDLES, (_lib.BFS_FOUND,), NO_PATH, extra=("max_width",),
                            reuse=lambda have, want: _wclass(have[0]) == _wclass(want[0]))
+# expand writes the candidates' number M, and the searches are over when there are none; a step
+# without a verdict adds a node to a search, and a search ends at its budget: budget + 2 steps
+_STEPS = _scored._Steps(_BEAM, "expand", "select", lambda M, _: (M, M), 2,
+                        (("nodes", np.int64), ("steps", np.int64)))
 
 
 def release_workspaces() -> None:
@@ -35,38 +37,12 @@ def release_workspaces() -> None:
     _batch_bfs._release(_BEAM)
 
 
-def _validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error, name):
-    """the first checks of every search scored by the caller (_batch_vgreedy.py too): (states,
-    budgets) or ValueError; no GPU call."""
-    states, budgets = _batch_bfs._validate(presentations, max_nodes_to_explore, on_error, name)
-    if not callable(scorer):
-        raise ValueError("scorer must be callable")
-    if scorer_input not in ("features", "tokens"):
-        raise ValueError(f"scorer_input must be 'features' or 'tokens', not {scorer_input!r}")
-    return states, budgets
-
-
-def _validate_norm(scorer_input, feat_mean, feat_std):
-    """their last checks: (mean, std) as float32 arrays or (None, None), or ValueError"""
-    if (feat_mean is None) != (feat_std is None):
-        raise ValueError("pass both feat_mean and feat_std, or neither")
-    mean = std = None
-    if feat_mean is not None:
-        if scorer_input != "features":
-            raise ValueError("feat_mean / feat_std go with scorer_input='features'")
-        mean, std = (np.ascontiguousarray(torch.as_tensor(x).detach().cpu().numpy(), dtype=np.float32)
-                     for x in (feat_mean, feat_std))
-        if mean.shape != (14,) or std.shape != (14,):
-            raise ValueError("feat_mean and feat_std hold 14 values each")
-    return mean, std
-
-
 def _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore, scorer_input, feat_mean, feat_std,
                    on_error):
     """(states, budgets, widths (N) int32, mean, std as float32 arrays or None) or ValueError; no
     GPU call."""
-    states, budgets = _validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error,
-                                       "beam_search_many")
+    states, budgets = _scored._validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error,
+                                               _BEAM.name)
     N = len(states)
     if np.ndim(beam_width) == 0:
         if isinstance(beam_width, (bool, np.bool_)) or not isinstance(beam_width, (int, np.integer)):
@@ -79,7 +55,7 @@ def _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore, scor
         w = w.astype(np.int64)
     if N and (int(w.min()) < 1 or int(w.max()) > MAX_WIDTH):
         raise ValueError(f"beam_width must lie in [1, {MAX_WIDTH}]")
-    mean, std = _validate_norm(scorer_input, feat_mean, feat_std)
+    mean, std = _scored._validate_norm(scorer_input, feat_mean, feat_std)
     return states, budgets, w.astype(np.int32), mean, std
 
 
@@ -105,76 +81,9 @@ def beam_search_many(presentations, scorer, beam_width=50, max_nodes_to_explore=
       free device memory); a larger batch runs as consecutive groups, each with its own steps."""
     states, budgets, widths, mean, std = _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore,
                                                         scorer_input, feat_mean, feat_std, on_error)
-    N, L = states.shape[0], states.shape[1] // 2
-    stats = dict(status=np.zeros(N, np.int32), nodes=np.zeros(N, np.int64), steps=np.zeros(N, np.int64))
-    results = [NO_PATH] * N
-    if N:
-        dev, lib, cyc = _batch_bfs._device(device), _lib.load(), bool(cyclically_reduce_after_moves)
-        cap, wcap = int(budgets.max()), int(widths.max())
-        group = _batch_bfs._group_size(_BEAM, lib, dev, L, cyc, N, cap, workspace_bytes, (wcap,))
-        for g0 in range(0, N, group):
-            g1 = min(N, g0 + group)
-            _run_group(lib, dev, L, cyc, states[g0:g1], budgets[g0:g1], widths[g0:g1], group, cap, wcap, scorer,
-                       scorer_input, mean, std, g0, stats, results)
-    nan = np.nonzero(stats["status"] == _lib.BEAM_NAN)[0]
-    if len(nan):
-        raise ValueError(f"beam_search_many: the scorer returned NaN in searches {nan.tolist()}")
-    _batch_bfs._check_status("acx_beam", stats["status"])
-    return _batch_bfs._finish(_BEAM, results, stats, on_error, return_stats)
-
-
-def _scores(scorer, x, M):
-    with torch.no_grad():
-        y = scorer(x)
-    if not isinstance(y, torch.Tensor) or y.device != x.device:
-        raise ValueError("the scorer must return a tensor on its input's device")
-    if y.shape not in ((M,), (M, 1)):
-        raise ValueError(f"the scorer must return ({M},) or ({M}, 1) values, not {tuple(y.shape)}")
-    return y.reshape(M).to(torch.float32).contiguous()
-
-
-def _run_group(lib, dev, L, cyc, states, budgets, widths, n_cap, cap, wcap, scorer, scorer_input, mean, std, g0,
-               stats, results):
-    n, kw = len(states), _lib.key_words(L)
-    h = _batch_bfs._handle(_BEAM, lib, dev, L, cyc, n_cap, cap, (wcap,))
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        st = torch.from_numpy(states).to(dev)
-        bd = torch.from_numpy(budgets).to(dev)
-        wd = torch.from_numpy(widths).to(dev)
-        mean_d, std_d = (None if x is None else torch.from_numpy(x).to(dev) for x in (mean, std))
-        total = torch.zeros(1, dtype=torch.int64, device=dev)
-        _lib.check(lib.acx_beam_begin(h, st.data_ptr(), bd.data_ptr(), wd.data_ptr(), n, stream), "acx_beam_begin")
-        mark = (lambda: None) if _TIMING is None else _TIMING.mark
-        # a step without a verdict adds a node to a search, and a search ends at its budget
-        for _ in range(cap + 2):
-            mark()
-            _lib.check(lib.acx_beam_expand(h, total.data_ptr(), stream), "acx_beam_expand")
-            mark()
-            M = int(total.item())  # the step's one host synchronisation
-            if M == 0:
-                break
-            keys = torch.empty((M, kw), dtype=torch.int64, device=dev)
-            _lib.check(lib.acx_beam_gather(h, keys.data_ptr(), M, stream), "acx_beam_gather")
-            if scorer_input == "features":
-                x = ops.features(keys=keys, L=L, mean=mean_d, std=std_d)
-            else:
-                x = ops.token_ids(keys=keys, L=L)
-            mark()
-            y = _scores(scorer, x, M)
-            mark()
-            _lib.check(lib.acx_beam_select(h, y.data_ptr(), M, stream), "acx_beam_select")
-            mark()
-        else:
-            raise _lib.ACXError("acx_beam: the searches did not end within their budgets")
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-        min_len = torch.empty(n, dtype=torch.int32, device=dev)
-        nodes, steps, plen = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
-        _lib.check(lib.acx_beam_finish(h, status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(),
-                                       plen.data_ptr(), stream), "acx_beam_finish")
-        stats["status"][g0:g0 + n] = _batch_bfs._read_results(_BEAM, lib, h, dev, stream, g0, status, plen, results)
-        stats["nodes"][g0:g0 + n] = nodes.cpu().numpy()
-        stats["steps"][g0:g0 + n] = steps.cpu().numpy()
+    return _scored._run(_STEPS, states, budgets, (widths,), (int(widths.max()),) if len(widths) else (), scorer,
+                        scorer_input, mean, std, cyclically_reduce_after_moves, device, workspace_bytes, on_error,
+                        return_stats)
 
 
 def beam_search(presentation, model, architecture="mlp", feat_mean=None, feat_std=None, beam_width=50,
@@ -195,13 +104,9 @@ def beam_search(presentation, model, architecture="mlp", feat_mean=None, feat_st
     mlp = architecture == "mlp"
     if mlp and (feat_mean is None or feat_std is None):
         raise ValueError("architecture='mlp' needs feat_mean and feat_std")
-
-    def scorer(x):
-        return torch.expm1(model(x).squeeze(-1))
-
     p = np.asarray(presentation)
-    res, st = beam_search_many(p.reshape(1, -1).astype(np.int32), scorer, beam_width=int(beam_width),
-                               max_nodes_to_explore=int(max_nodes_to_explore),
+    res, st = beam_search_many(p.reshape(1, -1).astype(np.int32), _scored._model_scorer(model),
+                               beam_width=int(beam_width), max_nodes_to_explore=int(max_nodes_to_explore),
                                cyclically_reduce_after_moves=cyclically_reduce_after_moves,
                                scorer_input="features" if mlp else "tokens", feat_mean=feat_mean if mlp else None,
                                feat_std=feat_std if mlp else None, device=device, on_error="raise",

@@ -10,17 +10,18 @@ and the once-per-pop budget test are exact, and the only floats are the scorer's
 from __future__ import annotations
 
 import numpy as np
-import torch
 
-from .. import _lib, ops
-from . import _batch_bfs
-from ._batch_beam import _scores, _validate_norm, _validate_scorer
+from .. import _lib
+from . import _batch_bfs, _scored
 
 _HANDLES = {}  # (device, L, cyclical) -> (handle, searches, max_nodes_each)
 NO_PATH = (False, [])
-_TIMING = None  # tools/bench_search_many.py: an object whose mark(phase) is called after each phase of a step
 
 _VGREEDY = _batch_bfs._Engine("value_guided_greedy_search_many", "acx_vgreedy", _HANDLES, (_lib.BFS_FOUND,), NO_PATH)
+# pop writes (M, live); M == 0 with live searches: pops whose children were all known.  A pop takes
+# one of a search's at most budget + 11 nodes off its heap: budget + 13 steps
+_STEPS = _scored._Steps(_VGREEDY, "pop", "push", lambda M, live: (M, live), 13,
+                        (("nodes", np.int64), ("steps", np.int64), ("min_length", np.int32)))
 
 
 def release_workspaces() -> None:
@@ -55,71 +56,11 @@ def value_guided_greedy_search_many(presentations, scorer, max_nodes_to_explore=
       min_length.
     workspace_bytes: the most device memory the searches' workspace may take (default: half of the
       free device memory); a larger batch runs as consecutive groups, each with its own steps."""
-    states, budgets = _validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error,
-                                       _VGREEDY.name)
-    mean, std = _validate_norm(scorer_input, feat_mean, feat_std)
-    N, L = states.shape[0], states.shape[1] // 2
-    stats = dict(status=np.zeros(N, np.int32), nodes=np.zeros(N, np.int64), steps=np.zeros(N, np.int64),
-                 min_length=np.zeros(N, np.int32))
-    results = [NO_PATH] * N
-    if N:
-        dev, lib, cyc = _batch_bfs._device(device), _lib.load(), bool(cyclically_reduce_after_moves)
-        cap = int(budgets.max())
-        group = _batch_bfs._group_size(_VGREEDY, lib, dev, L, cyc, N, cap, workspace_bytes)
-        for g0 in range(0, N, group):
-            g1 = min(N, g0 + group)
-            _run_group(lib, dev, L, cyc, states[g0:g1], budgets[g0:g1], group, cap, scorer, scorer_input, mean, std,
-                       g0, stats, results)
-    nan = np.nonzero(stats["status"] == _lib.BEAM_NAN)[0]
-    if len(nan):
-        raise ValueError(f"{_VGREEDY.name}: the scorer returned NaN in searches {nan.tolist()}")
-    _batch_bfs._check_status("acx_vgreedy", stats["status"])
-    return _batch_bfs._finish(_VGREEDY, results, stats, on_error, return_stats)
-
-
-def _run_group(lib, dev, L, cyc, states, budgets, n_cap, cap, scorer, scorer_input, mean, std, g0, stats, results):
-    n, kw = len(states), _lib.key_words(L)
-    h = _batch_bfs._handle(_VGREEDY, lib, dev, L, cyc, n_cap, cap)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        st = torch.from_numpy(states).to(dev)
-        bd = torch.from_numpy(budgets).to(dev)
-        mean_d, std_d = (None if x is None else torch.from_numpy(x).to(dev) for x in (mean, std))
-        pair = torch.zeros(2, dtype=torch.int64, device=dev)
-        _lib.check(lib.acx_vgreedy_begin(h, st.data_ptr(), bd.data_ptr(), n, stream), "acx_vgreedy_begin")
-        mark = (lambda phase: None) if _TIMING is None else _TIMING.mark
-        # a pop takes one of a search's at most budget + 11 nodes off its heap
-        for _ in range(cap + 13):
-            mark("between")
-            _lib.check(lib.acx_vgreedy_pop(h, pair.data_ptr(), stream), "acx_vgreedy_pop")
-            mark("pop")
-            M, live = pair.tolist()  # the step's one host synchronisation
-            if live == 0:
-                break
-            if M == 0:  # pops whose children were all known: nothing to score
-                continue
-            keys = torch.empty((M, kw), dtype=torch.int64, device=dev)
-            _lib.check(lib.acx_vgreedy_gather(h, keys.data_ptr(), M, stream), "acx_vgreedy_gather")
-            if scorer_input == "features":
-                x = ops.features(keys=keys, L=L, mean=mean_d, std=std_d)
-            else:
-                x = ops.token_ids(keys=keys, L=L)
-            mark("gather_features")
-            y = _scores(scorer, x, M)
-            mark("scorer")
-            _lib.check(lib.acx_vgreedy_push(h, y.data_ptr(), M, stream), "acx_vgreedy_push")
-            mark("push")
-        else:
-            raise _lib.ACXError("acx_vgreedy: the searches did not end within their budgets")
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-        min_len = torch.empty(n, dtype=torch.int32, device=dev)
-        nodes, steps, plen = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
-        _lib.check(lib.acx_vgreedy_finish(h, status.data_ptr(), nodes.data_ptr(), steps.data_ptr(),
-                                          min_len.data_ptr(), plen.data_ptr(), stream), "acx_vgreedy_finish")
-        stats["status"][g0:g0 + n] = _batch_bfs._read_results(_VGREEDY, lib, h, dev, stream, g0, status, plen, results)
-        stats["nodes"][g0:g0 + n] = nodes.cpu().numpy()
-        stats["steps"][g0:g0 + n] = steps.cpu().numpy()
-        stats["min_length"][g0:g0 + n] = min_len.cpu().numpy()
+    states, budgets = _scored._validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error,
+                                               _VGREEDY.name)
+    mean, std = _scored._validate_norm(scorer_input, feat_mean, feat_std)
+    return _scored._run(_STEPS, states, budgets, (), (), scorer, scorer_input, mean, std,
+                        cyclically_reduce_after_moves, device, workspace_bytes, on_error, return_stats)
 
 
 def _total_length(f):
@@ -150,10 +91,7 @@ def value_guided_greedy_search(presentation, model=None, architecture="mlp", fea
             raise ValueError("a model is needed unless use_length_priority=True")
         if mlp and (feat_mean is None or feat_std is None):
             raise ValueError("architecture='mlp' needs feat_mean and feat_std")
-
-        def scorer(x):
-            return torch.expm1(model(x).squeeze(-1))
-
+        scorer = _scored._model_scorer(model)
         kw = dict(scorer_input="features", feat_mean=feat_mean, feat_std=feat_std) if mlp else dict(scorer_input="tokens")
     p = np.asarray(presentation)
     res, st = value_guided_greedy_search_many(p.reshape(1, -1).astype(np.int32), scorer,

@@ -1,0 +1,136 @@
+"""What the batched searches scored by the caller share (_batch_beam.py, _batch_vgreedy.py; the
+step frame of csrc/acx_scored.h): the checks of the scorer's arguments, the scorer call, and the
+loop of steps -- make the candidates, read their count (the step's one host synchronisation),
+gather them, score them, hand the scores back."""
+
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+from . import _batch_bfs
+
+_TIMING = None  # tools/bench_search_many.py: an object whose mark(phase) is called after each phase of a step
+
+
+class _Steps:
+    """How an engine steps: its _Engine, the names of its two step calls (`make` the candidates,
+    `take` their scores: beam expand / select, vgreedy pop / push), `report`: what the two numbers
+    make wrote mean, as (M rows to score, live searches), the loop's bound beyond the largest budget
+    with its reason, and the stats it returns besides status."""
+
+    def __init__(self, eng, make, take, report, slack, stats):
+        self.eng, self.make, self.take, self.report, self.slack, self.stats = eng, make, take, report, slack, stats
+
+
+def _validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error, name):
+    """the first checks of every search scored by the caller: (states, budgets) or ValueError; no
+    GPU call."""
+    states, budgets = _batch_bfs._validate(presentations, max_nodes_to_explore, on_error, name)
+    if not callable(scorer):
+        raise ValueError("scorer must be callable")
+    if scorer_input not in ("features", "tokens"):
+        raise ValueError(f"scorer_input must be 'features' or 'tokens', not {scorer_input!r}")
+    return states, budgets
+
+
+def _validate_norm(scorer_input, feat_mean, feat_std):
+    """their last checks: (mean, std) as float32 arrays or (None, None), or ValueError"""
+    if (feat_mean is None) != (feat_std is None):
+        raise ValueError("pass both feat_mean and feat_std, or neither")
+    mean = std = None
+    if feat_mean is not None:
+        if scorer_input != "features":
+            raise ValueError("feat_mean / feat_std go with scorer_input='features'")
+        mean, std = (np.ascontiguousarray(torch.as_tensor(x).detach().cpu().numpy(), dtype=np.float32)
+                     for x in (feat_mean, feat_std))
+        if mean.shape != (14,) or std.shape != (14,):
+            raise ValueError("feat_mean and feat_std hold 14 values each")
+    return mean, std
+
+
+def _scores(scorer, x, M):
+    with torch.no_grad():
+        y = scorer(x)
+    if not isinstance(y, torch.Tensor) or y.device != x.device:
+        raise ValueError("the scorer must return a tensor on its input's device")
+    if y.shape not in ((M,), (M, 1)):
+        raise ValueError(f"the scorer must return ({M},) or ({M}, 1) values, not {tuple(y.shape)}")
+    return y.reshape(M).to(torch.float32).contiguous()
+
+
+def _model_scorer(model):
+    """the scorer of the single-search wrappers: _score_states_mlp / _score_states_seq of the reference"""
+    return lambda x: torch.expm1(model(x).squeeze(-1))
+
+
+def _run(sc, states, budgets, own, extra, scorer, scorer_input, mean, std, cyclical, device, workspace_bytes, on_error,
+         return_stats):
+    """the validated searches, in groups that fit the workspace -> the call's return value.  `own`:
+    the engine's per-search arrays for its begin call (beam: the widths), `extra`: its handle's
+    shape arguments."""
+    eng = sc.eng
+    N, L = states.shape[0], states.shape[1] // 2
+    stats = {k: np.zeros(N, t) for k, t in (("status", np.int32), *sc.stats)}
+    results = [eng.no_path] * N
+    if N:
+        dev, lib, cyc = _batch_bfs._device(device), _lib.load(), bool(cyclical)
+        cap = int(budgets.max())
+        group = _batch_bfs._group_size(eng, lib, dev, L, cyc, N, cap, workspace_bytes, extra)
+        for g0 in range(0, N, group):
+            g1 = min(N, g0 + group)
+            _run_group(sc, lib, dev, L, cyc, states[g0:g1], budgets[g0:g1], [x[g0:g1] for x in own], group, cap, extra,
+                       scorer, scorer_input, mean, std, g0, stats, results)
+    nan = np.nonzero(stats["status"] == _lib.BEAM_NAN)[0]
+    if len(nan):
+        raise ValueError(f"{eng.name}: the scorer returned NaN in searches {nan.tolist()}")
+    _batch_bfs._check_status(eng.prefix, stats["status"])
+    return _batch_bfs._finish(eng, results, stats, on_error, return_stats)
+
+
+def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, scorer, scorer_input, mean, std, g0,
+               stats, results):
+    eng = sc.eng
+    n, kw = len(states), _lib.key_words(L)
+    h = _batch_bfs._handle(eng, lib, dev, L, cyc, n_cap, cap, extra)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    call = lambda what, *args: _lib.check(eng.fn(lib, what)(h, *args, stream), f"{eng.prefix}_{what}")  # noqa: E731
+    with torch.cuda.device(dev):
+        st = torch.from_numpy(states).to(dev)
+        bd = torch.from_numpy(budgets).to(dev)
+        own_d = [torch.from_numpy(x).to(dev) for x in own]
+        mean_d, std_d = (None if x is None else torch.from_numpy(x).to(dev) for x in (mean, std))
+        out = torch.zeros(2, dtype=torch.int64, device=dev)
+        call("begin", st.data_ptr(), bd.data_ptr(), *(x.data_ptr() for x in own_d), n)
+        mark = (lambda phase: None) if _TIMING is None else _TIMING.mark
+        for _ in range(cap + sc.slack):
+            mark("between")
+            call(sc.make, out.data_ptr())
+            mark(sc.make)
+            M, live = sc.report(*out.tolist())  # the step's one host synchronisation
+            if live == 0:
+                break
+            if M == 0:  # nothing to score
+                continue
+            keys = torch.empty((M, kw), dtype=torch.int64, device=dev)
+            call("gather", keys.data_ptr(), M)
+            if scorer_input == "features":
+                x = ops.features(keys=keys, L=L, mean=mean_d, std=std_d)
+            else:
+                x = ops.token_ids(keys=keys, L=L)
+            mark("gather_features")
+            y = _scores(scorer, x, M)
+            mark("scorer")
+            call(sc.take, y.data_ptr(), M)
+            mark(sc.take)
+        else:
+            raise _lib.ACXError(f"{eng.prefix}: the searches did not end within their budgets")
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        min_len = torch.empty(n, dtype=torch.int32, device=dev)
+        nodes, steps, plen = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+        call("finish", status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(), plen.data_ptr())
+        stats["status"][g0:g0 + n] = _batch_bfs._read_results(eng, lib, h, dev, stream, g0, status, plen, results)
+        for k, v in (("nodes", nodes), ("steps", steps), ("min_length", min_len)):
+            if k in stats:
+                stats[k][g0:g0 + n] = v.cpu().numpy()

@@ -38,10 +38,12 @@
 // LDS by a bitonic network over the next power of two, CAP = 1024, 4096 or 16384 words by the
 // handle's max_width (8, 32, 128 KiB of LDS: the widest class holds one workgroup per CU, which is
 // why a handle of narrow beams does not use it).
+// The frame of a step -- the state's common fields, the offsets, the gather, the results copy and
+// the host bodies of begin / expand / gather / finish -- is acx_scored.h, shared with acx_vgreedy.hip.
 // Every loop is bounded: steps by the budget (a step without a verdict adds a node), passes by
 // max_width / 64, probes by nb, the path walk by the node count.
 //
-// Registers and LDS (hipcc --offload-arch=gfx950 -O3, the kernels' metadata in --save-temps):
+// Registers and LDS (tools/kernel_resources.py; every figure: profiles/heap_shared/kernel_resources.md):
 //   beam_expand_kernel<1 / 2 / 3 / 4 / 8>   82 / 88 / 90 / 92 / 126 VGPRs, 18,976 / 25,120 / 31,264 /
 //       37,408 / 6,684 B of LDS: 5, 5, 5, 4, 4 waves per SIMD, as mbfs_kernel (<2> also has 24 B of
 //       private memory per lane; the other widths have none);
@@ -53,18 +55,16 @@
 
 #include "acx_beam_key.h"
 #include "acx_round.h"
+#include "acx_scored.h"
 
 namespace acx {
 namespace beam {
 
 using namespace acx::round;
+using scored::ended;
 
-// a search between two launches
-struct State {
-    int64_t n_nodes, max_nodes, steps, cand_base;
-    int32_t done, beam_n, width, cand_n;
-    uint32_t running;  // min total of the root and the children looked at
-    int32_t pad;
+struct State : scored::State {
+    int32_t beam_n, width;  // entries of the beam, and the most it may hold
 };
 
 struct Args : round::Args {
@@ -75,16 +75,6 @@ struct Args : round::Args {
     int32_t max_width;
     int64_t n;  // searches of the running call
 };
-
-__device__ __forceinline__ void finish(const Args& a, int64_t q, State* S, int32_t status, int32_t act, int64_t node,
-                                       int64_t n_nodes, int64_t steps, uint32_t running, int64_t plen) {
-    batch::write_result(a, q, Res{status, act, node, 2, 0, n_nodes}, steps, running, plen);
-    S->done = 1;
-    S->n_nodes = n_nodes;
-    S->steps = steps;
-    S->cand_n = 0;
-    a.counts[q] = 0;
-}
 
 template <int NW>
 __global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* widths) {
@@ -101,7 +91,7 @@ __global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* 
     const bool wide = w < 1 || w > a.max_width;
     // (a search's results are written where it ends; until then, and for a width out of range:)
     if (!root.refused) batch::write_result(a, q, Res{ACX_MBFS_OVERFLOW, 0, 0, 0, 0, 0}, 0, 0, 0);
-    *S = State{1, root.max_nodes, 0, 1, root.refused || wide, 1, w, 0, root.total0, 0};
+    *S = State{{1, root.max_nodes, 0, 1, root.refused || wide, 0, root.total0, 0}, 1, w};
     a.beam[q * a.max_width] = 0;
     a.counts[q] = 0;
 }
@@ -130,7 +120,7 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
     if (tid == 0) r.s_over = 0;
     __syncthreads();  // the state is read before thread 0 rewrites it
     if (n_nodes >= max_nodes || beam_n < 1) {  // the reference's loop condition
-        if (tid == 0) finish(a, q, S, beam_n < 1 ? ACX_BFS_EXHAUSTED : ACX_BFS_BUDGET, 0, 0, n_nodes, steps, running, 0);
+        if (tid == 0) ended(a, q, S, beam_n < 1 ? ACX_BFS_EXHAUSTED : ACX_BFS_BUDGET, 0, 0, n_nodes, steps, running, 0);
         return;
     }
     ++steps;
@@ -229,9 +219,9 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
     if (status != 0) {
         // the edges to the success child's parent + (action, 2)
         const int64_t plen = status == ACX_BFS_FOUND ? batch::path_depth(meta, succ_node, a.rows) + 1 : 0;
-        finish(a, q, S, status, succ_act, succ_node, n_nodes, steps, running, plen);
+        ended(a, q, S, status, succ_act, succ_node, n_nodes, steps, running, plen);
     } else if (cand_n == 0) {  // the beam died
-        finish(a, q, S, ACX_BFS_EXHAUSTED, 0, 0, n_nodes, steps, running, 0);
+        ended(a, q, S, ACX_BFS_EXHAUSTED, 0, 0, n_nodes, steps, running, 0);
     } else {
         S->n_nodes = n_nodes;
         S->steps = steps;
@@ -240,36 +230,6 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
         S->running = running;
         a.counts[q] = (int32_t)cand_n;
     }
-}
-
-// offsets = exclusive prefix sum of counts (n + 1 entries), *total = their sum: one block
-__global__ __launch_bounds__(1024) void beam_offsets_kernel(Args a, int64_t* total) {
-    __shared__ uint32_t sh[1024 / WAVE];
-    int64_t run = 0;
-    for (int64_t b = 0; b < a.n; b += 1024) {
-        const int64_t i = b + threadIdx.x;
-        const uint32_t v = i < a.n ? (uint32_t)a.counts[i] : 0u;
-        uint32_t tot;
-        const uint32_t ex = block_excl_scan<1024>(v, sh, tot);
-        if (i < a.n) a.offsets[i] = run + ex;
-        run += tot;
-        __syncthreads();  // sh is rewritten by the next chunk
-    }
-    if (threadIdx.x == 0) {
-        a.offsets[a.n] = run;
-        *total = run;
-    }
-}
-
-// the candidates' keys of search q are consecutive rows of its store: one copy per search
-__global__ __launch_bounds__(TPB) void beam_gather_kernel(Args a, uint64_t* keys, int64_t M) {
-    const int64_t q = blockIdx.x;
-    const State* S = a.state + q;
-    const int64_t n = a.counts[q], off = a.offsets[q], base = S->cand_base;
-    if (n <= 0 || off < 0 || off + n > M || base < 0 || base + n > a.rows) return;
-    const uint64_t* src = a.store + (q * a.rows + base) * a.kw;
-    uint64_t* dst = keys + off * a.kw;
-    for (int64_t t = threadIdx.x; t < n * a.kw; t += TPB) dst[t] = src[t];
 }
 
 template <int CAP, int THREADS>
@@ -297,7 +257,7 @@ __global__ __launch_bounds__(THREADS) void beam_select_kernel(Args a, const floa
     }
     __syncthreads();
     if (s_nan) {  // (uniform) sticky: the search has ended, nothing is selected
-        if (tid == 0) finish(a, q, S, ACX_BEAM_NAN, 0, 0, S->n_nodes, S->steps, S->running, 0);
+        if (tid == 0) ended(a, q, S, ACX_BEAM_NAN, 0, 0, S->n_nodes, S->steps, S->running, 0);
         return;
     }
     for (int k = 2; k <= n2; k <<= 1) {
@@ -320,39 +280,25 @@ __global__ __launch_bounds__(THREADS) void beam_select_kernel(Args a, const floa
     if (tid == 0) S->beam_n = w;
 }
 
-__global__ __launch_bounds__(TPB) void beam_finish_kernel(Args a, int32_t* status, int64_t* nodes, int64_t* steps,
-                                                          int32_t* min_length, int64_t* path_len) {
-    const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (q >= a.n) return;
-    status[q] = a.status[q];
-    nodes[q] = a.nodes[q];
-    steps[q] = a.parents[q];
-    min_length[q] = a.min_length[q];
-    path_len[q] = a.path_len[q];
-}
-
-// what the handle (acx_batch.h) needs of this engine; max_width is set before arrays() is called
+// what the handle (acx_batch.h) and the step frame (acx_scored.h) need of this engine; max_width is
+// set before arrays() is called
 struct Engine {
     using Args = beam::Args;
     // a found search's path (value_guided_search.py:87-97,497-498): the edges + (action, 2), no root entry
     static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND;
     static constexpr bool ROOT_ENTRY = false;
+    static constexpr int GATHER_THREADS = TPB, MOST = 0;
+    static constexpr bool LIVE = false;
     static int64_t rows_for(int64_t B) { return B; }
     static uint32_t buckets_for(int64_t B) { return round::buckets_for(B); }
     template <class F>
     static void arrays(Args& a, F f) {
         round::arrays(a, f);
         f(a.beam, 4 * (size_t)a.max_width, false);
-        f(a.state, sizeof(State), true);  // (zeroed: done = 0 with no candidates before the first begin)
-        f(a.counts, 4, true);
-        f(a.offsets, 16, true);  // n + 1 entries
-        f(a.status, 4, true);
-        f(a.nodes, 8, true);
-        f(a.parents, 8, true);  // steps
-        f(a.min_length, 4, true);
-        f(a.path_len, 8, true);
+        scored::arrays(a, f);
     }
 };
+static_assert(sizeof(State) == 56 && scored::RECORD<State> == 140, "the bytes formula of include/acx.h");
 using Handle = batch::Handle<Engine>;
 
 static bool shape(Args& a, int32_t L, int64_t B, int32_t W, int32_t cyclical) {
@@ -363,8 +309,8 @@ static bool shape(Args& a, int32_t L, int64_t B, int32_t W, int32_t cyclical) {
 
 struct Begin {
     const Args& a;
-    const int32_t* widths;
     hipStream_t st;
+    const int32_t* widths;
     template <int NW>
     void go() { beam_begin_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a, widths); }
 };
@@ -380,6 +326,7 @@ struct Expand {
 
 namespace beam = acx::beam;
 namespace batch = acx::batch;
+namespace scored = acx::scored;
 using beam::Handle;
 
 extern "C" {
@@ -399,43 +346,21 @@ void acx_beam_destroy(void* h) { batch::destroy<beam::Engine>(h); }
 
 int acx_beam_begin(void* h, const int32_t* states, const int64_t* budgets, const int32_t* widths, int64_t n,
                    void* stream) {
-    Handle* S = static_cast<Handle*>(h);
-    if (!S || !states || !budgets || !widths || n < 0 || n > S->n_cap) return ACX_E_ARG;
-    beam::Args& a = S->a;
-    a.n = n;
-    if (n == 0) return ACX_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (!batch::new_epoch(S, st)) return ACX_E_LAUNCH;
-    a.states = states;
-    a.budgets = budgets;
-    acx::bfs::by_nw(a.L, beam::Begin{a, widths, st});
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return scored::begin<beam::Engine, beam::Begin>(h, states, budgets, widths != nullptr, n, stream, widths);
 }
 
 int acx_beam_expand(void* h, int64_t* total, void* stream) {
-    Handle* S = static_cast<Handle*>(h);
-    if (!S || !total) return ACX_E_ARG;
-    const beam::Args& a = S->a;
-    hipStream_t st = (hipStream_t)stream;
-    if (a.n > 0) acx::bfs::by_nw(a.L, beam::Expand{a, st});
-    beam::beam_offsets_kernel<<<dim3(1), dim3(1024), 0, st>>>(a, total);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return scored::make<beam::Engine, beam::Expand>(h, total, stream);
 }
 
 int acx_beam_gather(void* h, uint64_t* keys, int64_t M, void* stream) {
-    Handle* S = static_cast<Handle*>(h);
-    if (!S || M < 0 || (M > 0 && !keys)) return ACX_E_ARG;
-    const beam::Args& a = S->a;
-    if (a.n == 0 || M == 0) return ACX_OK;
-    beam::beam_gather_kernel<<<dim3((unsigned)a.n), dim3(acx::bfs::TPB), 0, (hipStream_t)stream>>>(a, keys, M);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return scored::gather<beam::Engine>(h, keys, M, stream);
 }
 
 int acx_beam_select(void* h, const float* scores, int64_t M, void* stream) {
-    Handle* S = static_cast<Handle*>(h);
-    if (!S || M < 0 || (M > 0 && !scores)) return ACX_E_ARG;
-    const beam::Args& a = S->a;
-    if (a.n == 0 || M == 0) return ACX_OK;
+    bool run;
+    if (const int e = scored::step_args<beam::Engine>(h, scores, M, &run); e != ACX_OK || !run) return e;
+    const beam::Args& a = static_cast<Handle*>(h)->a;
     hipStream_t st = (hipStream_t)stream;
     const int most = 12 * a.max_width;  // candidates of a step
     if (most <= 1024) beam::beam_select_kernel<1024, 256><<<dim3((unsigned)a.n), dim3(256), 0, st>>>(a, scores, M);
@@ -446,13 +371,7 @@ int acx_beam_select(void* h, const float* scores, int64_t M, void* stream) {
 
 int acx_beam_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, int32_t* min_length, int64_t* path_len,
                     void* stream) {
-    Handle* S = static_cast<Handle*>(h);
-    if (!S || !status || !nodes || !steps || !min_length || !path_len) return ACX_E_ARG;
-    const beam::Args& a = S->a;
-    if (a.n == 0) return ACX_OK;
-    beam::beam_finish_kernel<<<dim3((unsigned)((a.n + acx::bfs::TPB - 1) / acx::bfs::TPB)), dim3(acx::bfs::TPB), 0,
-                               (hipStream_t)stream>>>(a, status, nodes, steps, min_length, path_len);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return scored::finish<beam::Engine>(h, status, nodes, steps, min_length, path_len, stream);
 }
 
 int acx_beam_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,

@@ -7,10 +7,6 @@ tests/vgreedy_yardstick.py (checked on the CPU by test_vgreedy_cpu.py; here its 
 which is the engine's and which that file proves equal to the literal one).  A call has one scorer,
 so the fixture's records are grouped by (L, flag, scorer, normalisation)."""
 import functools
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,22 +14,14 @@ import torch
 
 import beam_yardstick as BY
 import vgreedy_yardstick as Y
-from conftest import REPO
 from many_common import AK2, _dataset_rows, _load, _norm, _same, _scrambled
 from test_gpu_batch_refusals import SENTINEL, _rows
 from test_gpu_batch_refusals import _check_search as _refusals_check_search
-from weak_hash_common import FATAL, check_classes, skip_after_death, variant
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 AK3 = [1, 1, 1, -2, -2, -2, -2, 1, 2, 1, -2, -1, -2]
-DEAD = []  # why the weak-hash child died: the tests after it are skipped
-
-
-@pytest.fixture(autouse=True)
-def _one_death_ends_the_module():
-    skip_after_death(DEAD)
 
 
 def _pad(letters, L, n0=7):
@@ -498,37 +486,3 @@ def test_a_push_with_the_wrong_m_ends_the_search_it_cannot_serve():
             _check_search(out, i, y)
     finally:
         lib.acx_vgreedy_destroy(h)
-
-
-# ---------------------------------------------------------------------------------------------
-# the visited set under a colliding hash (libacx_weakhash.so): last, in one fresh child process
-# ---------------------------------------------------------------------------------------------
-def test_under_the_colliding_hash(tmp_path):
-    """AK(3), a pop with twins and Miller-Schupp rows at L = 18, at most 2,000 nodes per search,
-    through the variant library in one child with one time limit: the results are those of the
-    shipped library in this process, and every search's nodes fall in at most 8 hash classes"""
-    twin = next(p for p, _, _, _ in Y.twin_cases() if len(p) == 36)
-    rows = [_pad(AK3, 18), twin] + list(_dataset_rows()[::40])
-    budgets = [1989, 600] + [1200] * (len(rows) - 2)
-    call = dict(pres=[r.tolist() for r in rows], scorer="S1", budgets=budgets, cyc=False)
-    with open(tmp_path / "in.json", "w") as f:
-        json.dump(call, f)
-    env = dict(os.environ, ACX_LIB=variant())
-    child = os.path.join(REPO, "tests", "vgreedy_weak_hash_child.py")
-    try:
-        r = subprocess.run([sys.executable, child, str(tmp_path)], env=env, capture_output=True, text=True, timeout=300)
-    except subprocess.TimeoutExpired as e:
-        DEAD.append(f"vgreedy weak-hash child: timeout: {str(e.stderr)[-2000:]}")
-        pytest.fail(DEAD[-1])
-    if r.returncode < 0 or r.returncode in FATAL:
-        DEAD.append(f"vgreedy weak-hash child: exit code {r.returncode}: {r.stderr[-2000:]}")
-        pytest.fail(DEAD[-1])
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    got = json.loads(r.stdout.strip().splitlines()[-1])
-    res, st = _many(np.stack(rows), "S1", budgets, on_error="return")
-    assert got["res"] == res and got["st"] == {k: v.tolist() for k, v in st.items()}
-    assert max(got["nodes"]) <= 2000 and got["nodes"] == [int(v) for v in st["nodes"]]
-    big = [(n, c) for n, c in zip(got["nodes"], got["classes"]) if n >= 512]
-    assert len(big) >= 3
-    for n, c in big:
-        check_classes(n, c, "vgreedy_many")

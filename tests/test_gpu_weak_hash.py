@@ -6,8 +6,9 @@ other states with its own fingerprint at every insert (false fingerprint matches
 compare decides), a chunk's lanes claim along that one chain, and stale entries of earlier epochs
 lie anywhere in it (tests/test_weak_hash_cpu.py pins those properties of the hash).  The searches
 must not change: the expected values are the reference's recorded runs (tests/golden), the
-yardsticks (tests/bfs_yardstick.py, tests/greedy_yardstick.py, tests/beam_yardstick.py) and the same calls made in this
-process through libacx.so -- never the variant's.
+yardsticks (tests/bfs_yardstick.py, tests/greedy_yardstick.py, tests/beam_yardstick.py,
+tests/vgreedy_yardstick.py) and the same calls made in this process through libacx.so -- never the
+variant's.
 
 The variant cannot share a process with libacx.so: each test hands its calls to one fresh child
 (tests/weak_hash_child.py), one at a time.  After a child that ended on a signal, an abort or its
@@ -28,8 +29,10 @@ import greedy_yardstick as YG
 import test_gpu_beam_many as TBM
 import test_gpu_bfs_many as TB
 import test_gpu_greedy_many as TG
+import test_gpu_vgreedy_many as TVM
+import vgreedy_yardstick as YV
 from conftest import GOLDEN
-from many_common import AK2, _check_records, _load
+from many_common import AK2, _check_records, _dataset_rows, _load
 from test_gpu_sbfs import _ak3, _check_cases, _extra_cases, _ms17
 from weak_hash_common import ChildDied, check_classes, run_child, skip_after_death
 
@@ -168,7 +171,7 @@ def test_device_bfs(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------
-# the batched engines (csrc/acx_mbfs.hip, csrc/acx_mgreedy.hip, csrc/acx_beam.hip)
+# the batched engines (csrc/acx_mbfs.hip, csrc/acx_mgreedy.hip, csrc/acx_beam.hip, csrc/acx_vgreedy.hip)
 # ---------------------------------------------------------------------------------------------
 def _check_many(answer, part, tag):
     """a call's answer against the yardstick's results y of its searches [(presentation, y)]"""
@@ -261,6 +264,25 @@ def test_beam_many(tmp_path):
     res, st = TBM._many(np.array(call["pres"], np.int32), "S0", 50, 3000)
     assert got["res"] == res and got["st"] == {k: v.tolist() for k, v in st.items()}
     assert st["nodes"][0] == got["nodes"][0] >= 512
+
+
+def test_vgreedy_many(tmp_path):
+    """AK(3), a pop with twins and Miller-Schupp rows at L = 18, at most 2,000 nodes per search,
+    through the variant library in one child with one time limit: the results are those of the
+    shipped library in this process, and every search's nodes fall in at most 8 hash classes"""
+    twin = next(p for p, _, _, _ in YV.twin_cases() if len(p) == 36)
+    rows = [TVM._pad(TVM.AK3, 18), twin] + list(_dataset_rows()[::40])
+    budgets = [1989, 600] + [1200] * (len(rows) - 2)
+    call = dict(op="vgreedy_many", pres=[r.tolist() for r in rows], scorer="S1", budgets=budgets, cyc=False)
+    out, _ = _job("vgreedy_many", [call], tmp_path, timeout=300)
+    got = out[0]
+    res, st = TVM._many(np.stack(rows), "S1", budgets, on_error="return")
+    assert got["res"] == res and got["st"] == {k: v.tolist() for k, v in st.items()}
+    assert max(got["nodes"]) <= BATCH_CAP and got["nodes"] == [int(v) for v in st["nodes"]]
+    big = [(n, c) for n, c in zip(got["nodes"], got["classes"]) if n >= 512]
+    assert len(big) >= 3
+    for n, c in big:
+        _report("vgreedy_many", "a search at L=18", n, c)
 
 
 # ---------------------------------------------------------------------------------------------

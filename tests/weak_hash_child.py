@@ -115,24 +115,35 @@ class Ops:
         import acx
         return self._many(acx.greedy_search_many, c)
 
-    def beam_many(self, i, c):
-        """the search's result and stats, and over its nodes (the yardstick's, packed on the CPU)
-        their count and the number of distinct key hashes"""
-        import acx
-        import beam_yardstick as Y
+    def _scored_many(self, fn, c, nodes_of, **kw):
+        """a scored search's results and stats, and over each search's nodes (the yardstick's:
+        nodes_of(presentation, its index), packed on the CPU) their count and the number of
+        distinct key hashes"""
         from weak_hash_common import pack_keys_np
         pres = np.array(c["pres"], np.int32)
         L = pres.shape[1] // 2
-        res, st = acx.beam_search_many(pres, Y.SCORERS[c["scorer"]][1], beam_width=c["W"], max_nodes_to_explore=c["budget"],
-                                       cyclically_reduce_after_moves=c["cyc"], device=self.dev, return_stats=True,
-                                       on_error="return")
+        res, st = fn(pres, cyclically_reduce_after_moves=c["cyc"], device=self.dev, return_stats=True, on_error="return",
+                     **kw)
         out = {"res": [None if r is None else [bool(r[0]), _path(r[1])] for r in res],
                "st": {k: v.tolist() for k, v in st.items()}, "nodes": [], "classes": []}
-        for p in pres:
-            states = np.stack(Y.beam(p, c["scorer"], c["W"], c["budget"], c["cyc"])["states"])
+        for j, p in enumerate(pres):
+            states = np.stack(nodes_of(p, j)["states"])
             out["nodes"].append(int(len(states)))
             out["classes"].append(_classes(self.lib, pack_keys_np(states, L), L)["classes"])
         return out
+
+    def beam_many(self, i, c):
+        import acx
+        import beam_yardstick as Y
+        return self._scored_many(acx.beam_search_many, c, lambda p, j: Y.beam(p, c["scorer"], c["W"], c["budget"], c["cyc"]),
+                                 scorer=Y.SCORERS[c["scorer"]][1], beam_width=c["W"], max_nodes_to_explore=c["budget"])
+
+    def vgreedy_many(self, i, c):
+        import acx
+        import vgreedy_yardstick as Y
+        return self._scored_many(acx.value_guided_greedy_search_many, c,
+                                 lambda p, j: Y.vgreedy(p, c["scorer"], c["budgets"][j], c["cyc"], drop_twins=True),
+                                 scorer=Y.SCORERS[c["scorer"]][1], max_nodes_to_explore=c["budgets"])
 
     def sbfs(self, i, c):
         """arena_log2_cap: on a fresh workspace whose key arena starts at 2^cap records (the

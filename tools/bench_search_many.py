@@ -113,28 +113,36 @@ def s0(f):
 
 
 class Marks:
-    """HIP events at the marks of _batch_beam._run_group: per step before / after expand, after
-    gather + features, after the scorer, after select (the last step ends after its expand)"""
-    NAMES = ("expand", "gather_features", "scorer", "select")
+    """HIP events at the marks of _scored._run_group: each mark names the phase that has just ended
+    ("between": the host's time from the end of a step to the next step's first launch); split()
+    gives the milliseconds of the phases in `names` and the steps (marks of the phase `step`)"""
 
-    def __init__(self):
-        self.ev = []
+    def __init__(self, step, names):
+        self.step, self.names, self.ev = step, names, []
 
-    def mark(self):
+    def mark(self, phase):
         e = torch.cuda.Event(enable_timing=True)
         e.record()
-        self.ev.append(e)
+        self.ev.append((phase, e))
 
     def split(self):
         torch.cuda.synchronize()
-        ms, steps, i = dict.fromkeys(self.NAMES, 0.0), 0, 0
-        while i + 1 < len(self.ev):
-            k = min(5, len(self.ev) - i)
-            for j in range(k - 1):
-                ms[self.NAMES[j]] += self.ev[i + j].elapsed_time(self.ev[i + j + 1])
-            steps += 1
-            i += k
-        return {"steps": steps, **{f"{n}_ms": v for n, v in ms.items()}}
+        ms = dict.fromkeys(self.names, 0.0)
+        for (_, a), (phase, b) in zip(self.ev, self.ev[1:]):
+            if phase in ms:
+                ms[phase] += a.elapsed_time(b)
+        return {"steps": sum(p == self.step for p, _ in self.ev), **{f"{n}_ms": v for n, v in ms.items()}}
+
+
+def split_of(many, step, names):
+    """the step split of one more run of `many`"""
+    from acx.search import _scored
+    marks = _scored._TIMING = Marks(step, names)
+    try:
+        many()
+    finally:
+        _scored._TIMING = None
+    return marks.split()
 
 
 def host_beam(rows, W, budget):
@@ -197,12 +205,7 @@ def bench_beam():
                                     return_stats=True)
 
     (batch_res, stats), batch_walls = timed(many, "batch")
-    marks = Marks()
-    _batch_beam._TIMING = marks
-    try:
-        many()
-    finally:
-        _batch_beam._TIMING = None
+    split = split_of(many, "expand", ("expand", "gather_features", "scorer", "select"))
     sub = rows[::5]
     host_beam(sub[:8], W, args.budget)  # warm-up
     torch.cuda.synchronize()
@@ -222,7 +225,7 @@ def bench_beam():
         "beam_died": int((stats["status"] == _lib.BFS_EXHAUSTED).sum()),
         "nodes_total": int(stats["nodes"].sum()), "steps_max": int(stats["steps"].max()),
         "batch_wall_ms": min(batch_walls) * 1e3, "batch_walls_ms": [w * 1e3 for w in batch_walls],
-        "batch_step_split_hip_events": marks.split(),
+        "batch_step_split_hip_events": split,
         "host_rows": len(sub), "host_wall_ms": host_wall * 1e3, "host_runs": 1,
         "host_wall_scaled_to_all_rows_ms": host_wall * 1e3 * N / len(sub),
         "host_scaled_note": f"the host-side search ran on every fifth row ({len(sub)}); its wall time is scaled by "
@@ -231,27 +234,6 @@ def bench_beam():
         "batch_workspace_bytes": int(h[1] * _lib.load().acx_beam_bytes(L, h[2], h[3])),
         "results_equal": True,
     }
-
-
-class PhaseMarks:
-    """HIP events at the marks of _batch_vgreedy._run_group: each mark names the phase that has just
-    ended ("between": the host's time from the end of a step to the next pop's launch)"""
-
-    def __init__(self):
-        self.ev = []
-
-    def mark(self, phase):
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        self.ev.append((phase, e))
-
-    def split(self):
-        torch.cuda.synchronize()
-        ms, steps = {}, 0
-        for (_, a), (phase, b) in zip(self.ev, self.ev[1:]):
-            ms[phase] = ms.get(phase, 0.0) + a.elapsed_time(b)
-            steps += phase == "pop"
-        return {"steps": steps, **{f"{n}_ms": v for n, v in sorted(ms.items())}}
 
 
 def host_vgreedy(rows, budget):
@@ -310,12 +292,7 @@ def bench_vgreedy():
                                                    return_stats=True)
 
     (batch_res, stats), batch_walls = timed(many, "batch")
-    marks = PhaseMarks()
-    _batch_vgreedy._TIMING = marks
-    try:
-        many()
-    finally:
-        _batch_vgreedy._TIMING = None
+    split = split_of(many, "pop", ("between", "gather_features", "pop", "push", "scorer"))
     sub = rows[::5]
     host_vgreedy(sub[:8], args.budget)  # warm-up
     torch.cuda.synchronize()
@@ -337,7 +314,7 @@ def bench_vgreedy():
         "nodes_total": int(stats["nodes"].sum()), "pops_total": int(stats["steps"].sum()),
         "pops_max": int(stats["steps"].max()),
         "batch_wall_ms": min(batch_walls) * 1e3, "batch_walls_ms": [w * 1e3 for w in batch_walls],
-        "batch_step_split_hip_events": marks.split(),
+        "batch_step_split_hip_events": split,
         "host_rows": len(sub), "host_wall_ms": host_wall * 1e3, "host_runs": 1,
         "host_wall_scaled_to_all_rows_ms": host_wall * 1e3 * N / len(sub),
         "host_scaled_note": f"the host-side search ran on every fifth row ({len(sub)}); its wall time is scaled by "
