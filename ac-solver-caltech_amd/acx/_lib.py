@@ -111,6 +111,8 @@ SIGNATURES = {
     # the hash seam of the search engines (csrc/acx_test_hash.h; tests only)
     "acx_internal_hash_classes": ([], ctypes.c_int32),
     "acx_internal_key_hash": ([_P, _I32], ctypes.c_uint64),
+    # the MCTS kernels' score routine over arrays (csrc/acx_mcts.hip; tests only)
+    "acx_internal_ucb": ([_P, _P, _P, ctypes.c_double, _P, _I64, _P], ctypes.c_int),
 }
 
 # the batched engines, one workgroup per search: BFS (ac-solver-caltech_amd/csrc/acx_mbfs.hip) and
@@ -151,6 +153,21 @@ SIGNATURES.update({
     "acx_vgreedy_finish": ([_P] * 7, ctypes.c_int),
     "acx_vgreedy_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
     "acx_vgreedy_destroy": ([_P], None),
+})
+
+# MCTS scored by the caller (ac-solver-caltech_amd/csrc/acx_mcts.hip): a step is select (with the
+# host's log table and the UCB1 constant), gather, the scorer, backup
+MCTS_SPIN = 64
+SIGNATURES.update({
+    "acx_mcts_bytes": ([_I32, _I64], ctypes.c_int64),
+    "acx_mcts_create": ([_I32, _I64, _I64, _I32], ctypes.c_void_p),
+    "acx_mcts_begin": ([_P, _P, _P, _I64, _P], ctypes.c_int),
+    "acx_mcts_select": ([_P, _P, _I64, ctypes.c_double, _P, _P], ctypes.c_int),
+    "acx_mcts_gather": ([_P, _P, _I64, _P], ctypes.c_int),
+    "acx_mcts_backup": ([_P, _P, _I64, _P], ctypes.c_int),
+    "acx_mcts_finish": ([_P] * 7, ctypes.c_int),
+    "acx_mcts_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
+    "acx_mcts_destroy": ([_P], None),
 })
 
 _lib = None

@@ -85,12 +85,13 @@ def _release(eng) -> None:
 
 
 def release_workspaces() -> None:
-    """Free the cached batch workspaces (the batched greedy, beam and value-guided greedy searches' too)."""
+    """Free the cached batch workspaces (the batched greedy, beam, value-guided greedy and MCTS searches' too)."""
     _release(_BFS)
-    from . import _batch_beam, _batch_greedy, _batch_vgreedy
+    from . import _batch_beam, _batch_greedy, _batch_mcts, _batch_vgreedy
     _batch_greedy.release_workspaces()
     _batch_beam.release_workspaces()
     _batch_vgreedy.release_workspaces()
+    _batch_mcts.release_workspaces()
 
 
 def _validate(presentations, max_nodes_to_explore, on_error, name="bfs_many"):

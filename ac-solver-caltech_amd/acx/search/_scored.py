@@ -1,4 +1,4 @@
-"""What the batched searches scored by the caller share (_batch_beam.py, _batch_vgreedy.py; the
+"""What the batched searches scored by the caller share (_batch_beam.py, _batch_vgreedy.py, _batch_mcts.py; the
 step frame of csrc/acx_scored.h): the checks of the scorer's arguments, the scorer call, and the
 loop of steps -- make the candidates, read their count (the step's one host synchronisation),
 gather them, score them, hand the scores back."""
@@ -16,12 +16,17 @@ _TIMING = None  # tools/bench_search_many.py: an object whose mark(phase) is cal
 
 class _Steps:
     """How an engine steps: its _Engine, the names of its two step calls (`make` the candidates,
-    `take` their scores: beam expand / select, vgreedy pop / push), `report`: what the two numbers
-    make wrote mean, as (M rows to score, live searches), the loop's bound beyond the largest budget
-    with its reason, and the stats it returns besides status."""
+    `take` their scores: beam expand / select, vgreedy pop / push, mcts select / backup), `report`: what the two numbers
+    make wrote mean, as (M rows to score, live searches), the loop's bound -- the steps beyond the
+    largest budget, or a function of the largest budget -- with its reason, and the stats it
+    returns besides status.  `make_args(dev, step, margs)`: the engine's own arguments of its make
+    call at step `step`, before the output pair (mcts: the log table and the constant), from what
+    its entry passed to _run as `margs`."""
 
-    def __init__(self, eng, make, take, report, slack, stats):
-        self.eng, self.make, self.take, self.report, self.slack, self.stats = eng, make, take, report, slack, stats
+    def __init__(self, eng, make, take, report, bound, stats, make_args=None):
+        self.eng, self.make, self.take, self.report, self.stats = eng, make, take, report, stats
+        self.bound = bound if callable(bound) else (lambda cap: cap + bound)
+        self.make_args = make_args
 
 
 def _validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error, name):
@@ -66,10 +71,10 @@ def _model_scorer(model):
 
 
 def _run(sc, states, budgets, own, extra, scorer, scorer_input, mean, std, cyclical, device, workspace_bytes, on_error,
-         return_stats):
+         return_stats, margs=None):
     """the validated searches, in groups that fit the workspace -> the call's return value.  `own`:
     the engine's per-search arrays for its begin call (beam: the widths), `extra`: its handle's
-    shape arguments."""
+    shape arguments, `margs`: what its _Steps.make_args needs."""
     eng = sc.eng
     N, L = states.shape[0], states.shape[1] // 2
     stats = {k: np.zeros(N, t) for k, t in (("status", np.int32), *sc.stats)}
@@ -81,7 +86,7 @@ def _run(sc, states, budgets, own, extra, scorer, scorer_input, mean, std, cycli
         for g0 in range(0, N, group):
             g1 = min(N, g0 + group)
             _run_group(sc, lib, dev, L, cyc, states[g0:g1], budgets[g0:g1], [x[g0:g1] for x in own], group, cap, extra,
-                       scorer, scorer_input, mean, std, g0, stats, results)
+                       scorer, scorer_input, mean, std, g0, stats, results, margs)
     nan = np.nonzero(stats["status"] == _lib.BEAM_NAN)[0]
     if len(nan):
         raise ValueError(f"{eng.name}: the scorer returned NaN in searches {nan.tolist()}")
@@ -90,7 +95,7 @@ def _run(sc, states, budgets, own, extra, scorer, scorer_input, mean, std, cycli
 
 
 def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, scorer, scorer_input, mean, std, g0,
-               stats, results):
+               stats, results, margs=None):
     eng = sc.eng
     n, kw = len(states), _lib.key_words(L)
     h = _batch_bfs._handle(eng, lib, dev, L, cyc, n_cap, cap, extra)
@@ -104,9 +109,9 @@ def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, sc
         out = torch.zeros(2, dtype=torch.int64, device=dev)
         call("begin", st.data_ptr(), bd.data_ptr(), *(x.data_ptr() for x in own_d), n)
         mark = (lambda phase: None) if _TIMING is None else _TIMING.mark
-        for _ in range(cap + sc.slack):
+        for step in range(sc.bound(cap)):
             mark("between")
-            call(sc.make, out.data_ptr())
+            call(sc.make, *(sc.make_args(dev, step, margs) if sc.make_args else ()), out.data_ptr())
             mark(sc.make)
             M, live = sc.report(*out.tolist())  # the step's one host synchronisation
             if live == 0:
@@ -131,6 +136,6 @@ def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, sc
         nodes, steps, plen = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
         call("finish", status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(), plen.data_ptr())
         stats["status"][g0:g0 + n] = _batch_bfs._read_results(eng, lib, h, dev, stream, g0, status, plen, results)
-        for k, v in (("nodes", nodes), ("steps", steps), ("min_length", min_len)):
+        for k, v in (("nodes", nodes), ("steps", steps), ("iterations", steps), ("min_length", min_len)):
             if k in stats:
                 stats[k][g0:g0 + n] = v.cpu().numpy()

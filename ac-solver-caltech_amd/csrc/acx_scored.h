@@ -1,10 +1,11 @@
-// acx_scored.h -- the step frame of the engines scored by the caller (acx_beam.hip, acx_vgreedy.hip):
-// a search lives between launches, and a step of all searches is
-//   make     the engine's kernel (beam: expand, vgreedy: pop): a live search's new nodes, rows
+// acx_scored.h -- the step frame of the engines scored by the caller (acx_beam.hip, acx_vgreedy.hip,
+// acx_mcts.hip): a search lives between launches, and a step of all searches is
+//   make     the engine's kernel (beam: expand, vgreedy: pop, mcts: select): a live search's new nodes, rows
 //            cand_base .. cand_base + cand_n of its store, are the step's candidates; then the
 //            offsets kernel turns the per-search counts into offsets and their sum M;
 //   gather   one contiguous copy per search into the caller's (M, kw) array, which the caller scores;
-//   (the engine's own second kernel -- beam: select, vgreedy: push -- reads scores[offsets[q] ..]).
+//   (the engine's own second kernel -- beam: select, vgreedy: push, mcts: backup -- reads
+//   scores[offsets[q] ..]).
 // A search that ends writes its results where it ends (ended) and has no candidates from then
 // on; finish() copies the results out.
 //
@@ -133,15 +134,16 @@ static int begin(void* h, const int32_t* states, const int64_t* budgets, bool ow
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 
-// the first half of a step: the engine's kernel (Launch{args, stream}) over the live searches, then
-// the offsets; out takes M (and, for an engine with LIVE, the live count)
-template <class E, class Launch>
-static int make(void* h, int64_t* out, void* stream) {
+// the first half of a step: the engine's kernel (Launch{args, stream, own...}, `own` the engine's
+// own arguments of the call: mcts) over the live searches, then the offsets; out takes M (and, for
+// an engine with LIVE, the live count)
+template <class E, class Launch, class... Own>
+static int make(void* h, int64_t* out, void* stream, Own... own) {
     batch::Handle<E>* S = static_cast<batch::Handle<E>*>(h);
     if (!S || !out) return ACX_E_ARG;
     const typename E::Args& a = S->a;
     hipStream_t st = (hipStream_t)stream;
-    if (a.n > 0) by_nw(a.L, Launch{a, st});
+    if (a.n > 0) by_nw(a.L, Launch{a, st, own...});
     offsets_kernel<typename E::Args, E::LIVE><<<dim3(1), dim3(1024), 0, st>>>(a, out);
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }

@@ -557,7 +557,7 @@ void acx_mgreedy_destroy(void* h);
  *   acx_beam_destroy frees the workspace.
  * All calls are asynchronous on `stream` and must use the same stream between begin and finish.
  */
-#define ACX_BEAM_NAN (-5) /* per-search status: the scorer returned NaN for one of its candidates (acx_vgreedy_* too) */
+#define ACX_BEAM_NAN (-5) /* per-search status: the scorer returned NaN for one of its candidates (acx_vgreedy_* too; acx_mcts_*: NaN or +inf) */
 #define ACX_BEAM_MAX_WIDTH 1024
 int64_t acx_beam_bytes(int32_t L, int64_t max_nodes_each, int32_t max_width);
 void* acx_beam_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t max_width, int32_t cyclical);
@@ -632,6 +632,69 @@ int acx_vgreedy_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps,
 int acx_vgreedy_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
                       void* stream);
 void acx_vgreedy_destroy(void* h);
+
+/*
+ * MCTS over a batch of presentations, scored by the caller (csrc/acx_mcts.hip): one wave owns one
+ * search -- node store, visited set and the tree's records (value sum, visit count, prior, the
+ * children's rows) -- on a private slice of the handle's workspace, and a step of all searches is
+ * acx_mcts_select, acx_mcts_gather, the caller's scorer on the gathered keys (acx_features /
+ * acx_token_ids read them as they are), acx_mcts_backup.  Given equal scores every search gives
+ * the result of mcts_search on its own presentation, value_search/mcts.py:177-314 with
+ * solution_cache=None and time_limit=None, decision for decision: the statistics are doubles and
+ * the UCB1 score is computed in the reference's operation order.  The root is not scored.
+ *   acx_mcts_bytes    (mcts.py:177-314) workspace bytes per search for budgets up to
+ *                     max_nodes_each = B at max_relator_length L, kw = acx_key_words(L):
+ *                       (8 kw + 36) (B + 11) + 64 ceil((B + 23) / 4) + 140
+ *                     (the rows -- key, parent, depth, a 24-byte record and a trail entry each; an
+ *                     iteration appends up to 12 nodes past the budget test --, the visited set,
+ *                     the search's state, its verdict record and its five results); ACX_E_ARG for
+ *                     L outside [1, ACX_MAX_L] or B outside [1, 2^24].
+ *   acx_mcts_create   (mcts.py:177-314) allocates n_searches times that on the current device;
+ *                     NULL on bad arguments or when the workspace does not fit.
+ *   acx_mcts_begin    (mcts.py:210-242) the roots of n <= n_searches searches: `states` DEVICE
+ *                     (n, 2L) int32, `budgets` DEVICE (n) int64 (a budget < 1 behaves as 1: no
+ *                     iteration is run).  A state outside the packed domain gets ACX_MBFS_DOMAIN,
+ *                     a budget above max_nodes_each ACX_MBFS_OVERFLOW; neither is searched.
+ *   acx_mcts_select   (mcts.py:244-289) iterations of every search that has not ended, until it
+ *                     has new children to score, ends, or has spent ACX_MCTS_SPIN iterations on
+ *                     dead ends (each backs up prior(leaf) + 50): the loop test, the descent by
+ *                     least prior among unvisited children and UCB1 among visited ones, the 12
+ *                     children, the raising test (ACX_BFS_MOVE_ERROR), the visited set, the
+ *                     trivial child (ACX_BFS_FOUND).  `log_table` DEVICE (n_log >= 2) double:
+ *                     log_table[k] = the host libm's log(k) for k >= 1; a search that meets a visit
+ *                     count >= n_log ends with ACX_MBFS_OVERFLOW.  `c_explore`: the UCB1
+ *                     constant, not a NaN.  `pair` DEVICE (2) int64 receives M, the candidates of
+ *                     all searches, and the number of searches that have not ended.  M == 0 with
+ *                     searches left is a step without a scorer call; no searches left ends the loop.
+ *   acx_mcts_gather   (mcts.py:127-151) `keys` DEVICE (M, kw) uint64: the candidates' packed keys
+ *                     in (search, candidate) order.
+ *   acx_mcts_backup   (mcts.py:153-154,297-298) `scores` DEVICE (M) float32 in that order: the
+ *                     priors max(score, 0) are stored, and the least of a search's is backed up
+ *                     from the expanded leaf to the root.  A NaN or +inf among a search's scores
+ *                     ends it with ACX_BEAM_NAN.  M must be the value acx_mcts_select wrote: a
+ *                     search whose candidates do not fit M ends with ACX_MBFS_OVERFLOW.
+ *   acx_mcts_finish   (mcts.py:304-314) outputs DEVICE arrays of n: status (an ACX_BFS_* value --
+ *                     ACX_BFS_BUDGET: len(visited) reached the budget, ACX_BFS_EXHAUSTED: 50 *
+ *                     budget iterations -- or a negative refusal), nodes (nodes_explored),
+ *                     iterations, min_length (the root's total), path_len.
+ *   acx_mcts_paths    (mcts.py:166-174) for every search with ACX_BFS_FOUND the reference's path
+ *                     [(action, total), ..., (action, 2)] (no root entry; empty for a trivial root)
+ *                     in CSR form at offsets[q], as acx_mbfs_paths writes its paths.
+ *   acx_mcts_destroy  frees the workspace.
+ * All calls are asynchronous on `stream` and must use the same stream between begin and finish.
+ */
+#define ACX_MCTS_SPIN 64
+int64_t acx_mcts_bytes(int32_t L, int64_t max_nodes_each);
+void* acx_mcts_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int32_t cyclical);
+int acx_mcts_begin(void* h, const int32_t* states, const int64_t* budgets, int64_t n, void* stream);
+int acx_mcts_select(void* h, const double* log_table, int64_t n_log, double c_explore, int64_t* pair, void* stream);
+int acx_mcts_gather(void* h, uint64_t* keys, int64_t M, void* stream);
+int acx_mcts_backup(void* h, const float* scores, int64_t M, void* stream);
+int acx_mcts_finish(void* h, int32_t* status, int64_t* nodes, int64_t* iterations, int32_t* min_length,
+                    int64_t* path_len, void* stream);
+int acx_mcts_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
+                   void* stream);
+void acx_mcts_destroy(void* h);
 
 /*
  * Breadth-first search with the node store and the visited set partitioned over G GPUs by key
@@ -783,9 +846,13 @@ const char* acx_version(void);
  *   acx_internal_hash_classes  0 in the shipped library, K in such a build
  *   acx_internal_key_hash      the hash the device engines' visited sets and the sbfs owner
  *                              rule take of a packed key of L's key words (HOST pointer; the
- *                              host value of bfs::khash); 0 on a bad argument */
+ *                              host value of bfs::khash); 0 on a bad argument
+ *   acx_internal_ucb           the MCTS kernels' own score routine over DEVICE arrays of n:
+ *                              out[i] = -(sum[i] / visit[i]) + c * sqrt(logN[i] / visit[i]) */
 int32_t acx_internal_hash_classes(void);
 uint64_t acx_internal_key_hash(const uint64_t* key, int32_t L);
+int acx_internal_ucb(const double* sum, const uint32_t* visit, const double* logN, double c, double* out, int64_t n,
+                     void* stream);
 
 #ifdef __cplusplus
 }

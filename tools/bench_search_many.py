@@ -2,7 +2,7 @@
 budget 10^4, not cyclical -- what the reference's trivialize_miller_schupp_through_search (and, for
 greedy, scripts/parallel_search.py) does, one search per presentation.
 
-    python tools/bench_search_many.py --engine bfs|greedy|beam|vgreedy [--budget N] [--rows N] [--out PATH]
+    python tools/bench_search_many.py --engine bfs|greedy|beam|vgreedy|mcts [--budget N] [--rows N] [--out PATH]
 
 Once as a loop of acx.bfs / acx.greedy_search with engine="device" (one search per call,
 csrc/acx_bfs.hip / csrc/acx_greedy.hip) and once as one acx.bfs_many / acx.greedy_search_many call
@@ -32,7 +32,16 @@ Beside it the same search written with the parent commit's public API -- ops.exp
 step over every live search's popped node, the children copied to the host, the heaps (heapq) and the
 visited sets in Python -- on every fifth row (238), run once after a warm-up on 8 rows and scaled as
 for the beam.  The results of those 238 rows must be equal.  Writes
-profiles/vgreedy_many/bench_vgreedy_many.json."""
+profiles/vgreedy_many/bench_vgreedy_many.json.
+
+--engine mcts: the same rows through one acx.mcts_search_many call (csrc/acx_mcts.hip), c_explore
+1.41, the value of a node = its total length, timed the same way, with the split of a step into
+select, gather + features, scorer and backup from HIP events of a further run.  Beside it the same
+search written with the parent commit's public API -- ops.expand12 once per iteration over every
+live search's selected leaf, the children copied to the host, the trees (visit counts, value sums,
+UCB1 with math.log), the visited sets and the backups in Python -- on every fifth row (238), run once
+after a warm-up on 8 rows and scaled as for the beam.  The results of those 238 rows must be equal.
+Writes profiles/mcts_many/bench_mcts_many.json."""
 import argparse
 import contextlib
 import io
@@ -61,7 +70,7 @@ ENGINES = {
 }
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--engine", choices=sorted(ENGINES) + ["beam", "vgreedy"], required=True)
+ap.add_argument("--engine", choices=sorted(ENGINES) + ["beam", "vgreedy", "mcts"], required=True)
 ap.add_argument("--width", type=int, default=50, help="beam width (--engine beam)")
 ap.add_argument("--budget", type=int, default=10 ** 4)
 ap.add_argument("--rows", type=int, default=0, help="only the first N presentations (0: all)")
@@ -325,6 +334,136 @@ def bench_vgreedy():
     }
 
 
+class _Tree:
+    """one search of host_mcts: the reference's nodes as parallel lists"""
+
+    def __init__(self, row):
+        self.states, self.total = [row], [int(np.count_nonzero(row))]
+        self.parent, self.action, self.children = [None], [None], [[]]
+        self.visit, self.vsum, self.prior = [1], [0.0], [0.0]
+        self.visited, self.iterations = {row.tobytes()}, 0
+
+    def select(self, c):
+        import math
+        node = 0
+        while self.children[node]:
+            kids = self.children[node]
+            unvisited = [k for k in kids if self.visit[k] == 0]
+            if unvisited:
+                node = min(unvisited, key=self.prior.__getitem__)
+                continue
+            best, logn = -math.inf, math.log(self.visit[node])
+            for k in kids:
+                score = -(self.vsum[k] / self.visit[k]) + c * math.sqrt(logn / self.visit[k])
+                if score > best:
+                    best, node_k = score, k
+            node = node_k
+        return node
+
+    def back_up(self, node, value):
+        while node is not None:
+            self.visit[node] += 1
+            self.vsum[node] += value
+            node = self.parent[node]
+
+    def path(self, node):
+        p = []
+        while self.parent[node] is not None:
+            p.append((self.action[node], self.total[node]))
+            node = self.parent[node]
+        return p[::-1]
+
+
+def host_mcts(rows, budget, c):
+    """mcts_search of every row, the value of a node its total length, with ops.expand12 as the only
+    device call (one per iteration, over the selected leaf of every live search): [(ok, path)],
+    nodes, iterations"""
+    trees = [_Tree(r) for r in rows]
+    res, live = [(False, [])] * len(rows), list(range(len(rows)))
+    while live:
+        live = [q for q in live if len(trees[q].visited) < budget and trees[q].iterations < 50 * budget]
+        if not live:
+            break
+        leaves = []
+        for q in live:
+            trees[q].iterations += 1
+            leaves.append(trees[q].select(c))
+        par = torch.from_numpy(np.stack([trees[q].states[v] for q, v in zip(live, leaves)])).to(dev)
+        out = acx.ops.expand12(par, cyclical=False)
+        ch, lens, err = (out[k].cpu().numpy() for k in ("children", "lengths", "err"))
+        tot = lens.sum(2)
+        assert not err.any()
+        nxt = []
+        for j, (q, leaf) in enumerate(zip(live, leaves)):
+            t, new = trees[q], []
+            for a in range(12):
+                state = ch[j, a].astype(np.int32)
+                key = state.tobytes()
+                if key in t.visited:
+                    continue
+                t.visited.add(key)
+                nid = len(t.states)
+                t.states.append(state)
+                t.total.append(int(tot[j, a]))
+                t.parent.append(leaf)
+                t.action.append(a)
+                t.children.append([])
+                t.visit.append(0)
+                t.vsum.append(0.0)
+                t.prior.append(float(tot[j, a]))  # the scorer: the total length
+                t.children[leaf].append(nid)
+                new.append(nid)
+            trivial = [v for v in new if t.total[v] == 2]
+            if trivial:
+                res[q] = (True, t.path(trivial[0]))
+                continue
+            t.back_up(leaf, min(t.prior[v] for v in new) if new else t.prior[leaf] + 50)
+            nxt.append(q)
+        live = nxt
+    return res, [len(t.visited) for t in trees], [t.iterations for t in trees]
+
+
+def bench_mcts():
+    from acx.search import _batch_mcts
+    C = 1.41
+
+    def many(r=rows):
+        return acx.mcts_search_many(r, s0, max_nodes_to_explore=args.budget, c_explore=C, device=dev, return_stats=True)
+
+    (batch_res, stats), batch_walls = timed(many, "batch")
+    split = split_of(many, "select", ("between", "gather_features", "select", "backup", "scorer"))
+    sub = rows[::5]
+    host_mcts(sub[:8], args.budget, C)  # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    host_res, host_nodes, host_iters = host_mcts(sub, args.budget, C)
+    host_wall = time.perf_counter() - t0
+    print(f"host: {host_wall * 1e3:.2f} ms for {len(sub)} rows", file=sys.stderr, flush=True)
+    assert norm(host_res) == norm(batch_res[::5]), "mcts_search_many and the host-side search disagree"
+    assert np.array_equal(stats["nodes"][::5], np.array(host_nodes))
+    assert np.array_equal(stats["iterations"][::5], np.array(host_iters))
+    h = _batch_mcts._HANDLES[(0, L, False)]
+    return {
+        "workload": f"mcts_search of {N} Miller-Schupp presentations, L = {L}, budget {args.budget}, c_explore {C}, "
+                    "value = total length, not cyclical",
+        "device": torch.cuda.get_device_name(dev),
+        "searches": N, "solved": int(sum(bool(r[0]) for r in batch_res)),
+        "left_on_budget": int((stats["status"] == _lib.BFS_BUDGET).sum()),
+        "iteration_cap_reached": int((stats["status"] == _lib.BFS_EXHAUSTED).sum()),
+        "nodes_total": int(stats["nodes"].sum()), "iterations_total": int(stats["iterations"].sum()),
+        "iterations_max": int(stats["iterations"].max()),
+        "batch_wall_ms": min(batch_walls) * 1e3, "batch_walls_ms": [w * 1e3 for w in batch_walls],
+        "batch_step_split_hip_events": split,
+        "host_rows": len(sub), "host_wall_ms": host_wall * 1e3, "host_runs": 1,
+        "host_wall_scaled_to_all_rows_ms": host_wall * 1e3 * N / len(sub),
+        "host_scaled_note": f"the host-side search ran on every fifth row ({len(sub)}); its wall time is scaled by "
+                            f"{N}/{len(sub)} to stand beside the batch call",
+        "host_scaled_over_batch": host_wall * N / len(sub) / min(batch_walls),
+        "batch_workspace_bytes": int(h[1] * _lib.load().acx_mcts_bytes(L, h[2])),
+        "results_equal": True,
+    }
+
+
 def write(out):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
@@ -333,8 +472,8 @@ def write(out):
     print(json.dumps(out))
 
 
-if args.engine in ("beam", "vgreedy"):
-    write(bench_beam() if args.engine == "beam" else bench_vgreedy())
+if args.engine in ("beam", "vgreedy", "mcts"):
+    write({"beam": bench_beam, "vgreedy": bench_vgreedy, "mcts": bench_mcts}[args.engine]())
     sys.exit(0)
 
 (loop_res, loop_nodes), loop_walls = timed(loop, "loop")
