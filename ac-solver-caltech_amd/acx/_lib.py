@@ -126,49 +126,29 @@ for _prefix in ("acx_mbfs", "acx_mgreedy"):
     for _what, _args, _res in _BATCH:
         SIGNATURES[f"{_prefix}_{_what}"] = (_args, _res)
 
-# beam search scored by the caller (ac-solver-caltech_amd/csrc/acx_beam.hip): a step is expand,
-# gather, the scorer, select
+# the engines scored by the caller (the step frame of csrc/acx_scored.h): a step is the make call,
+# gather, the scorer, the take call.  Beam search (acx_beam.hip): expand, select.  Value-guided greedy
+# (acx_vgreedy.hip): pop, push; a NaN score ends a search with BEAM_NAN, as in the beam search.
+# MCTS (acx_mcts.hip): select (with the host's log table, its length and the UCB1 constant), backup.
+# Per engine: its make and take names, and its own arguments of the shape (bytes, create), of
+# begin and of the make call
 BEAM_NAN, BEAM_MAX_WIDTH = -5, 1024
-SIGNATURES.update({
-    "acx_beam_bytes": ([_I32, _I64, _I32], ctypes.c_int64),
-    "acx_beam_create": ([_I32, _I64, _I64, _I32, _I32], ctypes.c_void_p),
-    "acx_beam_begin": ([_P, _P, _P, _P, _I64, _P], ctypes.c_int),
-    "acx_beam_expand": ([_P, _P, _P], ctypes.c_int),
-    "acx_beam_gather": ([_P, _P, _I64, _P], ctypes.c_int),
-    "acx_beam_select": ([_P, _P, _I64, _P], ctypes.c_int),
-    "acx_beam_finish": ([_P] * 7, ctypes.c_int),
-    "acx_beam_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
-    "acx_beam_destroy": ([_P], None),
-})
-
-# value-guided greedy scored by the caller (ac-solver-caltech_amd/csrc/acx_vgreedy.hip): a step is
-# pop, gather, the scorer, push; a NaN score ends a search with BEAM_NAN, as in the beam search
-SIGNATURES.update({
-    "acx_vgreedy_bytes": ([_I32, _I64], ctypes.c_int64),
-    "acx_vgreedy_create": ([_I32, _I64, _I64, _I32], ctypes.c_void_p),
-    "acx_vgreedy_begin": ([_P, _P, _P, _I64, _P], ctypes.c_int),
-    "acx_vgreedy_pop": ([_P, _P, _P], ctypes.c_int),
-    "acx_vgreedy_gather": ([_P, _P, _I64, _P], ctypes.c_int),
-    "acx_vgreedy_push": ([_P, _P, _I64, _P], ctypes.c_int),
-    "acx_vgreedy_finish": ([_P] * 7, ctypes.c_int),
-    "acx_vgreedy_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
-    "acx_vgreedy_destroy": ([_P], None),
-})
-
-# MCTS scored by the caller (ac-solver-caltech_amd/csrc/acx_mcts.hip): a step is select (with the
-# host's log table and the UCB1 constant), gather, the scorer, backup
 MCTS_SPIN = 64
-SIGNATURES.update({
-    "acx_mcts_bytes": ([_I32, _I64], ctypes.c_int64),
-    "acx_mcts_create": ([_I32, _I64, _I64, _I32], ctypes.c_void_p),
-    "acx_mcts_begin": ([_P, _P, _P, _I64, _P], ctypes.c_int),
-    "acx_mcts_select": ([_P, _P, _I64, ctypes.c_double, _P, _P], ctypes.c_int),
-    "acx_mcts_gather": ([_P, _P, _I64, _P], ctypes.c_int),
-    "acx_mcts_backup": ([_P, _P, _I64, _P], ctypes.c_int),
-    "acx_mcts_finish": ([_P] * 7, ctypes.c_int),
-    "acx_mcts_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
-    "acx_mcts_destroy": ([_P], None),
-})
+_SCORED = (("acx_beam", "expand", "select", [_I32], [_P], []),
+           ("acx_vgreedy", "pop", "push", [], [], []),
+           ("acx_mcts", "select", "backup", [], [], [_P, _I64, ctypes.c_double]))
+for _prefix, _make, _take, _shape, _begin, _own in _SCORED:
+    SIGNATURES.update({
+        f"{_prefix}_bytes": ([_I32, _I64] + _shape, ctypes.c_int64),
+        f"{_prefix}_create": ([_I32, _I64, _I64] + _shape + [_I32], ctypes.c_void_p),
+        f"{_prefix}_begin": ([_P, _P, _P] + _begin + [_I64, _P], ctypes.c_int),
+        f"{_prefix}_{_make}": ([_P] + _own + [_P, _P], ctypes.c_int),
+        f"{_prefix}_gather": ([_P, _P, _I64, _P], ctypes.c_int),
+        f"{_prefix}_{_take}": ([_P, _P, _I64, _P], ctypes.c_int),
+        f"{_prefix}_finish": ([_P] * 7, ctypes.c_int),
+        f"{_prefix}_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
+        f"{_prefix}_destroy": ([_P], None),
+    })
 
 _lib = None
 

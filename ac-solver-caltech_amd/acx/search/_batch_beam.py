@@ -99,17 +99,8 @@ def beam_search(presentation, model, architecture="mlp", feat_mean=None, feat_st
     visited set, the budget cut, the stable selection -- is exact.
 
     solution_cache and time_limit are accepted only as None; verbose prints nothing."""
-    if solution_cache is not None or time_limit is not None:
-        raise NotImplementedError("acx.beam_search supports solution_cache=None and time_limit=None only")
-    mlp = architecture == "mlp"
-    if mlp and (feat_mean is None or feat_std is None):
-        raise ValueError("architecture='mlp' needs feat_mean and feat_std")
-    p = np.asarray(presentation)
-    res, st = beam_search_many(p.reshape(1, -1).astype(np.int32), _scored._model_scorer(model),
-                               beam_width=int(beam_width), max_nodes_to_explore=int(max_nodes_to_explore),
-                               cyclically_reduce_after_moves=cyclically_reduce_after_moves,
-                               scorer_input="features" if mlp else "tokens", feat_mean=feat_mean if mlp else None,
-                               feat_std=feat_std if mlp else None, device=device, on_error="raise",
-                               return_stats=True)
-    solved, path = res[0]
-    return solved, path, {"nodes_explored": int(st["nodes"][0]), "steps": int(st["steps"][0])}
+    solved, path, st = _scored._single(
+        "beam_search", beam_search_many, presentation, model, architecture, feat_mean, feat_std, solution_cache,
+        time_limit, dict(beam_width=beam_width, max_nodes_to_explore=max_nodes_to_explore),
+        cyclically_reduce_after_moves=cyclically_reduce_after_moves, device=device)
+    return solved, path, {"nodes_explored": st["nodes"], "steps": st["steps"]}

@@ -108,20 +108,8 @@ def mcts_search(presentation, model, architecture="mlp", feat_mean=None, feat_st
     are exact.  The root is not scored.
 
     solution_cache and time_limit are accepted only as None; verbose prints nothing."""
-    if solution_cache is not None or time_limit is not None:
-        raise NotImplementedError("acx.mcts_search supports solution_cache=None and time_limit=None only")
-    if model is None:
-        raise ValueError("a model is needed")
-    if architecture == "mlp":
-        if feat_mean is None or feat_std is None:
-            raise ValueError("architecture='mlp' needs feat_mean and feat_std")
-        kw = dict(scorer_input="features", feat_mean=feat_mean, feat_std=feat_std)
-    else:
-        kw = dict(scorer_input="tokens")
-    p = np.asarray(presentation)
-    res, st = mcts_search_many(p.reshape(1, -1).astype(np.int32), _scored._model_scorer(model),
-                               max_nodes_to_explore=int(max_nodes_to_explore), c_explore=c_explore,
-                               cyclically_reduce_after_moves=cyclically_reduce_after_moves, device=device,
-                               on_error="raise", return_stats=True, **kw)
-    solved, path = res[0]
-    return solved, path, {"nodes_explored": int(st["nodes"][0]), "iterations": int(st["iterations"][0])}
+    solved, path, st = _scored._single(
+        "mcts_search", mcts_search_many, presentation, model, architecture, feat_mean, feat_std, solution_cache,
+        time_limit, dict(max_nodes_to_explore=max_nodes_to_explore), no_model="a model is needed",
+        c_explore=c_explore, cyclically_reduce_after_moves=cyclically_reduce_after_moves, device=device)
+    return solved, path, {"nodes_explored": st["nodes"], "iterations": st["iterations"]}

@@ -81,22 +81,10 @@ def value_guided_greedy_search(presentation, model=None, architecture="mlp", fea
     expansion order, the visited set and the budget test are exact.  The root is not scored.
 
     solution_cache and time_limit are accepted only as None; verbose prints nothing."""
-    if solution_cache is not None or time_limit is not None:
-        raise NotImplementedError("acx.value_guided_greedy_search supports solution_cache=None and time_limit=None only")
-    mlp = architecture == "mlp"
-    if use_length_priority:
-        scorer, kw = _total_length, {}
-    else:
-        if model is None:
-            raise ValueError("a model is needed unless use_length_priority=True")
-        if mlp and (feat_mean is None or feat_std is None):
-            raise ValueError("architecture='mlp' needs feat_mean and feat_std")
-        scorer = _scored._model_scorer(model)
-        kw = dict(scorer_input="features", feat_mean=feat_mean, feat_std=feat_std) if mlp else dict(scorer_input="tokens")
-    p = np.asarray(presentation)
-    res, st = value_guided_greedy_search_many(p.reshape(1, -1).astype(np.int32), scorer,
-                                              max_nodes_to_explore=int(max_nodes_to_explore),
-                                              cyclically_reduce_after_moves=cyclically_reduce_after_moves,
-                                              device=device, on_error="raise", return_stats=True, **kw)
-    solved, path = res[0]
-    return solved, path, {"nodes_explored": int(st["nodes"][0]), "min_length": int(st["min_length"][0])}
+    solved, path, st = _scored._single(
+        "value_guided_greedy_search", value_guided_greedy_search_many, presentation, model, architecture, feat_mean,
+        feat_std, solution_cache, time_limit, dict(max_nodes_to_explore=max_nodes_to_explore),
+        no_model="a model is needed unless use_length_priority=True",
+        scorer=_total_length if use_length_priority else None,
+        cyclically_reduce_after_moves=cyclically_reduce_after_moves, device=device)
+    return solved, path, {"nodes_explored": st["nodes"], "min_length": st["min_length"]}

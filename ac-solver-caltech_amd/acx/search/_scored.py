@@ -1,7 +1,8 @@
 """What the batched searches scored by the caller share (_batch_beam.py, _batch_vgreedy.py, _batch_mcts.py; the
-step frame of csrc/acx_scored.h): the checks of the scorer's arguments, the scorer call, and the
-loop of steps -- make the candidates, read their count (the step's one host synchronisation),
-gather them, score them, hand the scores back."""
+step frame of csrc/acx_scored.h): the checks of the scorer's arguments, the scorer call, the body
+of their reference-signature wrappers of one search, and the loop of steps -- make the candidates,
+read their count (the step's one host synchronisation), gather them, score them, hand the scores
+back."""
 
 from __future__ import annotations
 
@@ -68,6 +69,30 @@ def _scores(scorer, x, M):
 def _model_scorer(model):
     """the scorer of the single-search wrappers: _score_states_mlp / _score_states_seq of the reference"""
     return lambda x: torch.expm1(model(x).squeeze(-1))
+
+
+def _single(name, many, presentation, model, architecture, feat_mean, feat_std, solution_cache, time_limit, ints,
+            no_model=None, scorer=None, **kw):
+    """A reference-signature wrapper `name` around its batch call `many`: one row, on_error="raise"
+    -> (solved, path, {stat: its int}).  `no_model`: the message when `model` is None (None: not
+    checked), `scorer`: one to use on the raw features in place of the model's (`model` and
+    `architecture` are then not looked at), `ints`: the keywords of `many` the reference takes as ints."""
+    if solution_cache is not None or time_limit is not None:
+        raise NotImplementedError(f"acx.{name} supports solution_cache=None and time_limit=None only")
+    if scorer is None:
+        if no_model is not None and model is None:
+            raise ValueError(no_model)
+        if architecture != "mlp":
+            kw["scorer_input"] = "tokens"
+        elif feat_mean is None or feat_std is None:
+            raise ValueError("architecture='mlp' needs feat_mean and feat_std")
+        else:
+            kw.update(scorer_input="features", feat_mean=feat_mean, feat_std=feat_std)
+        scorer = _model_scorer(model)
+    p = np.asarray(presentation)
+    res, st = many(p.reshape(1, -1).astype(np.int32), scorer, on_error="raise", return_stats=True,
+                   **{k: int(v) for k, v in ints.items()}, **kw)
+    return (*res[0], {k: int(v[0]) for k, v in st.items()})
 
 
 def _run(sc, states, budgets, own, extra, scorer, scorer_input, mean, std, cyclical, device, workspace_bytes, on_error,

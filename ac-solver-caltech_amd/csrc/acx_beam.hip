@@ -299,7 +299,6 @@ struct Engine {
     }
 };
 static_assert(sizeof(State) == 56 && scored::RECORD<State> == 140, "the bytes formula of include/acx.h");
-using Handle = batch::Handle<Engine>;
 
 static bool shape(Args& a, int32_t L, int64_t B, int32_t W, int32_t cyclical) {
     if (W < 1 || W > ACX_BEAM_MAX_WIDTH) return false;
@@ -327,7 +326,6 @@ struct Expand {
 namespace beam = acx::beam;
 namespace batch = acx::batch;
 namespace scored = acx::scored;
-using beam::Handle;
 
 extern "C" {
 
@@ -358,15 +356,12 @@ int acx_beam_gather(void* h, uint64_t* keys, int64_t M, void* stream) {
 }
 
 int acx_beam_select(void* h, const float* scores, int64_t M, void* stream) {
-    bool run;
-    if (const int e = scored::step_args<beam::Engine>(h, scores, M, &run); e != ACX_OK || !run) return e;
-    const beam::Args& a = static_cast<Handle*>(h)->a;
-    hipStream_t st = (hipStream_t)stream;
-    const int most = 12 * a.max_width;  // candidates of a step
-    if (most <= 1024) beam::beam_select_kernel<1024, 256><<<dim3((unsigned)a.n), dim3(256), 0, st>>>(a, scores, M);
-    else if (most <= 4096) beam::beam_select_kernel<4096, 1024><<<dim3((unsigned)a.n), dim3(1024), 0, st>>>(a, scores, M);
-    else beam::beam_select_kernel<16384, 1024><<<dim3((unsigned)a.n), dim3(1024), 0, st>>>(a, scores, M);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return scored::take<beam::Engine>(h, scores, M, stream, [=](const beam::Args& a, hipStream_t st) {
+        const int most = 12 * a.max_width;  // candidates of a step
+        if (most <= 1024) beam::beam_select_kernel<1024, 256><<<dim3((unsigned)a.n), dim3(256), 0, st>>>(a, scores, M);
+        else if (most <= 4096) beam::beam_select_kernel<4096, 1024><<<dim3((unsigned)a.n), dim3(1024), 0, st>>>(a, scores, M);
+        else beam::beam_select_kernel<16384, 1024><<<dim3((unsigned)a.n), dim3(1024), 0, st>>>(a, scores, M);
+    });
 }
 
 int acx_beam_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, int32_t* min_length, int64_t* path_len,

@@ -414,14 +414,7 @@ struct Engine {
     static uint32_t buckets_for(int64_t B) { return pop::buckets_for(B); }
     template <class F>
     static void arrays(Args& a, F f) {
-        const size_t R = (size_t)a.rows;
-        f(a.store, 8 * (size_t)a.kw * R, false);
-        f(a.meta, 4 * R, false);
-        f(a.depth, 4 * R, false);
-        f(a.rec, sizeof(Rec) * R, false);
-        f(a.trail, 4 * R, false);
-        f(a.table, 8 * (size_t)BUCKET * a.nb, true);
-        f(a.res, sizeof(Res), true);
+        pop::arrays(a, f, a.rec, sizeof(Rec), a.trail, 4);
         scored::arrays(a, f);
     }
 };
@@ -475,11 +468,9 @@ int acx_mcts_gather(void* h, uint64_t* keys, int64_t M, void* stream) {
 }
 
 int acx_mcts_backup(void* h, const float* scores, int64_t M, void* stream) {
-    bool run;
-    if (const int e = scored::step_args<Engine>(h, scores, M, &run); e != ACX_OK || !run) return e;
-    const mcts::Args& a = static_cast<batch::Handle<Engine>*>(h)->a;
-    mcts::mcts_backup_kernel<<<dim3((unsigned)a.n), dim3(mcts::GT), 0, (hipStream_t)stream>>>(a, scores, M);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return scored::take<Engine>(h, scores, M, stream, [=](const mcts::Args& a, hipStream_t st) {
+        mcts::mcts_backup_kernel<<<dim3((unsigned)a.n), dim3(mcts::GT), 0, st>>>(a, scores, M);
+    });
 }
 
 int acx_mcts_finish(void* h, int32_t* status, int64_t* nodes, int64_t* iterations, int32_t* min_length,

@@ -233,7 +233,7 @@ struct Engine {
     static int64_t rows_for(int64_t B) { return pop::rows_for(B); }
     static uint32_t buckets_for(int64_t B) { return pop::buckets_for(B); }
     template <class F>
-    static void arrays(Args& a, F f) { pop::arrays(a, f); }
+    static void arrays(Args& a, F f) { pop::arrays(a, f, a.hk, 8, a.hid, 4); }
     template <int NW>
     static void launch(const Args& a, int64_t n, hipStream_t st) {
         mgreedy_kernel<NW><<<dim3((unsigned)n), dim3(GT), 0, st>>>(a);

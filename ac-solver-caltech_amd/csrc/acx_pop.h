@@ -1,10 +1,14 @@
-// acx_pop.h -- what a pop of the heap engines has in common (acx_mgreedy.hip, acx_vgreedy.hip): one
-// wave owns one search; a pop takes the least entry off the search's heap (acx_heap.h), makes the
-// node's 12 children, looks at them in the reference's per-child order and appends the new ones.
+// acx_pop.h -- what a step of the one-wave-per-search engines has in common (acx_mgreedy.hip,
+// acx_vgreedy.hip, acx_mcts.hip): the engine picks a node -- the heap engines, mgreedy and vgreedy,
+// the least entry of the search's heap; mcts the leaf of a descent of its tree -- makes the node's 12
+// children, looks at them in the reference's per-child order and appends the new ones.
 //
-// Here: the slice's shape (rows_for, buckets_for, arrays), expand and append.  The insert between
-// them stays written in each kernel: as a shared routine it cost mgreedy_kernel<8> 14 VGPRs
-// (profiles/batch_shared/kernel_resources.md), and the two differ in which lanes insert.
+// Here: the slice's shape (rows_for, buckets_for, arrays), expand, survivors and append.  Args'
+// hk / hid and acx_heap.h are the heap engines' only; mcts has its records and its trail in their
+// place.  The insert between expand and append stays written in each kernel: as a shared routine
+// it cost mgreedy_kernel<8> 14 VGPRs (profiles/batch_shared/kernel_resources.md), and, shared by
+// the two scored engines alone, mcts_select_kernel<8> 12 (87 -> 99: a wave per SIMD less;
+// profiles/mcts/kernel_resources.md); greedy also differs in which lanes insert.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,15 +41,16 @@ struct Args : batch::Args {  // (depth is batch::Args's)
 inline int64_t rows_for(int64_t B) { return B + OVERSHOOT; }
 inline uint32_t buckets_for(int64_t B) { return (uint32_t)((2 * (rows_for(B) + 12) + BUCKET - 1) / BUCKET); }
 
-// the arrays every heap engine has, for its Engine::arrays (acx_batch.h)
-template <class A, class F>
-void arrays(A& a, F f) {
+// a slice's arrays, for the engine's Engine::arrays (acx_batch.h); o1, o2: the engine's own two, of
+// b1, b2 bytes per row (the heap engines' hk, hid; mcts's rec, trail)
+template <class A, class F, class O1, class O2>
+void arrays(A& a, F f, O1*& o1, size_t b1, O2*& o2, size_t b2) {
     const size_t R = (size_t)a.rows;
     f(a.store, 8 * (size_t)a.kw * R, false);
     f(a.meta, 4 * R, false);
     f(a.depth, 4 * R, false);
-    f(a.hk, 8 * R, false);
-    f(a.hid, 4 * R, false);
+    f(o1, b1 * R, false);
+    f(o2, b2 * R, false);
     f(a.table, 8 * (size_t)BUCKET * a.nb, true);
     f(a.res, sizeof(Res), true);
 }

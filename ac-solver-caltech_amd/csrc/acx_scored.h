@@ -115,8 +115,8 @@ static __global__ __launch_bounds__(TPB) void results_kernel(batch::Args a, int6
     path_len[q] = a.path_len[q];
 }
 
-// host: the bodies of an engine's acx_*_begin, its make call, _gather and _finish.  A run of n
-// searches begins: own_ok is the engine's check of its own arguments `own`, Launch{args, stream,
+// host: the bodies of an engine's acx_*_begin, its make call, _gather, its take call and _finish.
+// A run of n searches begins: own_ok is the engine's check of its own arguments `own`, Launch{args, stream,
 // own...} the by_nw functor of its begin kernel
 template <class E, class Launch, class... Own>
 static int begin(void* h, const int32_t* states, const int64_t* budgets, bool own_ok, int64_t n, void* stream,
@@ -165,6 +165,15 @@ static int gather(void* h, uint64_t* keys, int64_t M, void* stream) {
     const typename E::Args& a = static_cast<batch::Handle<E>*>(h)->a;
     gather_kernel<typename E::Args, E::GATHER_THREADS, E::MOST>
         <<<dim3((unsigned)a.n), dim3(E::GATHER_THREADS), 0, (hipStream_t)stream>>>(a, keys, M);
+    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+}
+
+// the second half of a step: launch(args, stream) is the engine's second kernel over the scores
+template <class E, class Launch>
+static int take(void* h, const float* scores, int64_t M, void* stream, Launch launch) {
+    bool run;
+    if (const int e = step_args<E>(h, scores, M, &run); e != ACX_OK || !run) return e;
+    launch(static_cast<batch::Handle<E>*>(h)->a, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 

@@ -286,7 +286,7 @@ struct Engine {
     static uint32_t buckets_for(int64_t B) { return pop::buckets_for(B); }
     template <class F>
     static void arrays(Args& a, F f) {
-        pop::arrays(a, f);
+        pop::arrays(a, f, a.hk, 8, a.hid, 4);
         scored::arrays(a, f);
     }
 };
@@ -334,11 +334,9 @@ int acx_vgreedy_gather(void* h, uint64_t* keys, int64_t M, void* stream) {
 }
 
 int acx_vgreedy_push(void* h, const float* scores, int64_t M, void* stream) {
-    bool run;
-    if (const int e = scored::step_args<Engine>(h, scores, M, &run); e != ACX_OK || !run) return e;
-    const vgreedy::Args& a = static_cast<batch::Handle<Engine>*>(h)->a;
-    vgreedy::vgreedy_push_kernel<<<dim3((unsigned)a.n), dim3(vgreedy::GT), 0, (hipStream_t)stream>>>(a, scores, M);
-    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
+    return scored::take<Engine>(h, scores, M, stream, [=](const vgreedy::Args& a, hipStream_t st) {
+        vgreedy::vgreedy_push_kernel<<<dim3((unsigned)a.n), dim3(vgreedy::GT), 0, st>>>(a, scores, M);
+    });
 }
 
 int acx_vgreedy_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, int32_t* min_length,

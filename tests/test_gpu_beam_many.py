@@ -15,21 +15,13 @@ import torch
 
 import beam_yardstick as Y
 from many_common import AK2, _dataset_rows, _load, _norm, _same, _scrambled
-from test_gpu_batch_refusals import SENTINEL, _rows
+from scored_common import AK3, Engine, _FnModel, _pad, _refused, _solvable, drive
 from test_gpu_batch_refusals import _check_search as _refusals_check_search
+from test_gpu_batch_refusals import _rows
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-AK3 = [1, 1, 1, -2, -2, -2, -2, 1, 2, 1, -2, -1, -2]
-
-
-def _pad(letters, L, n0=7):
-    s = np.zeros(2 * L, np.int32)
-    s[:n0], s[L:L + len(letters) - n0] = letters[:n0], letters[n0:]
-    return s
-
-
 def _many(pres, scorer, W, budgets, cyc=False, **kw):
     import acx
     fn = Y.SCORERS[scorer][1] if isinstance(scorer, str) else scorer
@@ -164,11 +156,6 @@ def test_more_searches_than_resident_workgroups():
         _check_yardstick(res, st, j, Y.beam(rows[j], "S0", 5, 100), j)
 
 
-def _solvable():
-    recs = [c for c in _load("greedy_many.json")["solvable"] if not c["cyclical"]][:40]
-    return np.array([c["presentation"] for c in recs]), [200 + 20 * (i % 7) for i in range(len(recs))]
-
-
 def test_split_call_equals_unsplit_call():
     from acx import _lib
     from acx.search import _batch_beam as B
@@ -269,15 +256,6 @@ def test_every_scored_record_grouped_into_single_calls():
                         [c["budget"] for c in recs], cyc, **kw)
         for i, c in enumerate(recs):
             _check_record(res, st, i, c)
-
-
-class _FnModel(torch.nn.Module):
-    def __init__(self, fn):
-        super().__init__()
-        self.fn = fn
-
-    def forward(self, x):
-        return self.fn(x)[:, None]
 
 
 @pytest.mark.parametrize("arch", ["mlp", "seq"])
@@ -439,40 +417,12 @@ def test_scorer_that_raises_mid_run_propagates(contract):
 # ---------------------------------------------------------------------------------------------
 # the C-ABI: refusal statuses, and the calls of a step one by one
 # ---------------------------------------------------------------------------------------------
+BEAM = Engine("acx_beam", "expand", "select", lambda cap: cap + 2, report=lambda M, _: (M, M))
+
+
 def _drive(lib, h, states, budgets, widths, L, scorer="S0"):
-    from acx import _lib, ops
-    n, kw = len(states), _lib.key_words(L)
-    stream = torch.cuda.current_stream(DEV).cuda_stream
-    fn = Y.SCORERS[scorer][1]
-    with torch.cuda.device(DEV):
-        st = torch.from_numpy(np.ascontiguousarray(states, np.int32)).to(DEV)
-        bd = torch.tensor(budgets, dtype=torch.int64, device=DEV)
-        wd = torch.tensor(widths, dtype=torch.int32, device=DEV)
-        total = torch.zeros(1, dtype=torch.int64, device=DEV)
-        assert lib.acx_beam_begin(h, st.data_ptr(), bd.data_ptr(), wd.data_ptr(), n, stream) == 0
-        for _ in range(max(budgets) + 2):
-            assert lib.acx_beam_expand(h, total.data_ptr(), stream) == 0
-            M = int(total.item())
-            if M == 0:
-                break
-            keys = torch.empty((M, kw), dtype=torch.int64, device=DEV)
-            assert lib.acx_beam_gather(h, keys.data_ptr(), M, stream) == 0
-            y = fn(ops.features(keys=keys, L=L)).to(torch.float32).contiguous()
-            assert lib.acx_beam_select(h, y.data_ptr(), M, stream) == 0
-        else:
-            raise AssertionError("the searches did not end")
-        status, min_len = (torch.full((n,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(2))
-        nodes, steps, plen = (torch.full((n,), SENTINEL, dtype=torch.int64, device=DEV) for _ in range(3))
-        assert lib.acx_beam_finish(h, status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(),
-                                   plen.data_ptr(), stream) == 0
-        out = dict(status=status.cpu().numpy(), nodes=nodes.cpu().numpy(), steps=steps.cpu().numpy(),
-                   min_length=min_len.cpu().numpy(), path_len=plen.cpu().numpy())
-        stride = int(out["path_len"].max()) + 3
-        offsets = torch.arange(n, dtype=torch.int64, device=DEV) * stride
-        acts, tots = (torch.full((n * stride,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(2))
-        assert lib.acx_beam_paths(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), n * stride, stream) == 0
-        out["acts"], out["tots"] = acts.cpu().numpy().reshape(n, stride), tots.cpu().numpy().reshape(n, stride)
-    return out
+    return drive(lib, h, BEAM, states, budgets, L, Y.SCORERS[scorer][1],
+                 begin=(torch.tensor(widths, dtype=torch.int32, device=DEV),))
 
 
 def _check_search(out, i, y):
@@ -500,8 +450,7 @@ def test_refused_searches_through_the_c_abi(L):
                 _lib.MBFS_OVERFLOW, _lib.MBFS_OVERFLOW, 0]
         for i, w in enumerate(want):
             if w < 0:
-                assert out["status"][i] == w and (out["acts"][i] == SENTINEL).all(), i
-                assert (out["nodes"][i], out["steps"][i], out["min_length"][i], out["path_len"][i]) == (0, 0, 0, 0), i
+                _refused(out, i, w)
             else:
                 _check_search(out, i, Y.beam(batch[i], "S0", widths[i], budgets[i]))
         # the epoch: the same handle, seven valid rows -- a refused search left nothing behind

@@ -15,21 +15,13 @@ import torch
 import mcts_yardstick as Y
 import vgreedy_yardstick as YV
 from many_common import AK2, _dataset_rows, _load, _norm, _same, _scrambled
-from test_gpu_batch_refusals import SENTINEL, _rows
+from scored_common import AK3, Engine, _FnModel, _key, _pad, _refused, _solvable, _thirteen, drive
 from test_gpu_batch_refusals import _check_search as _refusals_check_search
+from test_gpu_batch_refusals import _rows
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-AK3 = [1, 1, 1, -2, -2, -2, -2, 1, 2, 1, -2, -1, -2]
-
-
-def _pad(letters, L, n0=7):
-    s = np.zeros(2 * L, np.int32)
-    s[:n0], s[L:L + len(letters) - n0] = letters[:n0], letters[n0:]
-    return s
-
-
 def _fn(scorer):
     """a name of Y.MODELS / Y.TOKEN_MODELS: the model's output taken as the value itself (exact in
     float32 on both sides, no expm1), or a function"""
@@ -92,15 +84,6 @@ def test_every_fixture_record_grouped_into_single_calls(Ls, capsys):
     assert capsys.readouterr().out == ""  # mcts_search_many prints nothing
 
 
-class _FnModel(torch.nn.Module):
-    def __init__(self, fn):
-        super().__init__()
-        self.fn = fn
-
-    def forward(self, x):
-        return self.fn(x)[:, None]
-
-
 @pytest.mark.parametrize("group", ["ak", "c roots raise long", "ms", "norm"])
 def test_fixture_records_through_mcts_search(group):
     """the reference's signature, the model's output through expm1 on the GPU.  Float32 expm1 there
@@ -137,10 +120,6 @@ def test_fixture_records_through_mcts_search(group):
 @functools.lru_cache(maxsize=None)
 def _yard(key, scorer, budget, cyc=False, c=1.41):
     return Y.mcts(np.frombuffer(key, np.int32), Y.model_np(scorer), budget, c, cyc, on_tokens=scorer in Y.TOKEN_MODELS)
-
-
-def _key(p):
-    return np.ascontiguousarray(p, np.int32).tobytes()
 
 
 def _against_yardstick(pres, scorer, budgets, cyc=False, c=1.41, **kw):
@@ -313,11 +292,6 @@ def test_more_searches_than_resident_workgroups():
         _check_yardstick(res, st, j, _yard(_key(rows[j]), "M0", 60), j)
 
 
-def _solvable():
-    recs = [c for c in _load("greedy_many.json")["solvable"] if not c["cyclical"]][:40]
-    return np.array([c["presentation"] for c in recs]), [200 + 20 * (i % 7) for i in range(len(recs))]
-
-
 def test_split_call_equals_unsplit_call():
     from acx import _lib
     from acx.search import _batch_mcts as V
@@ -430,57 +404,20 @@ def test_scorer_contract_on_a_cached_handle():
 # ---------------------------------------------------------------------------------------------
 # the C-ABI: refusal statuses, and the calls of a step one by one
 # ---------------------------------------------------------------------------------------------
+MCTS = Engine("acx_mcts", "select", "backup", lambda cap: cap + 50 * cap // 64 + 3, steps="iterations")
+
+
 def _drive(lib, h, states, budgets, L, scorer="M0", short_backup_at=None, n_log=None, c=1.41):
     """short_backup_at: the step (0-based) whose backup is told M - 1 instead of M; n_log: the
     entries of the log table the select calls are told of (default: all it can need)"""
-    from acx import _lib, ops
-    n, kw = len(states), _lib.key_words(L)
-    stream = torch.cuda.current_stream(DEV).cuda_stream
-    fn = Y.model_t(scorer)
-    cap = max(budgets)
-    bound = cap + 50 * cap // 64 + 3
-    with torch.cuda.device(DEV):
-        st = torch.from_numpy(np.ascontiguousarray(states, np.int32)).to(DEV)
-        bd = torch.tensor(budgets, dtype=torch.int64, device=DEV)
-        pair = torch.zeros(2, dtype=torch.int64, device=DEV)
-        logs = torch.tensor([-math.inf] + [math.log(k) for k in range(1, 64 * (bound + 1) + 2)], dtype=torch.float64,
-                            device=DEV)
-        assert lib.acx_mcts_begin(h, st.data_ptr(), bd.data_ptr(), n, stream) == 0
-        for step in range(bound):
-            assert lib.acx_mcts_select(h, logs.data_ptr(), n_log or logs.numel(), c, pair.data_ptr(), stream) == 0
-            M, live = pair.tolist()
-            if live == 0:
-                assert M == 0
-                break
-            if M == 0:
-                continue
-            keys = torch.empty((M, kw), dtype=torch.int64, device=DEV)
-            assert lib.acx_mcts_gather(h, keys.data_ptr(), M, stream) == 0
-            y = fn(ops.features(keys=keys, L=L)).to(torch.float32).contiguous()
-            assert lib.acx_mcts_backup(h, y.data_ptr(), M - (step == short_backup_at), stream) == 0
-        else:
-            raise AssertionError("the searches did not end")
-        status, min_len = (torch.full((n,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(2))
-        nodes, iters, plen = (torch.full((n,), SENTINEL, dtype=torch.int64, device=DEV) for _ in range(3))
-        assert lib.acx_mcts_finish(h, status.data_ptr(), nodes.data_ptr(), iters.data_ptr(), min_len.data_ptr(),
-                                   plen.data_ptr(), stream) == 0
-        out = dict(status=status.cpu().numpy(), nodes=nodes.cpu().numpy(), iterations=iters.cpu().numpy(),
-                   min_length=min_len.cpu().numpy(), path_len=plen.cpu().numpy())
-        stride = int(out["path_len"].max()) + 3
-        offsets = torch.arange(n, dtype=torch.int64, device=DEV) * stride
-        acts, tots = (torch.full((n * stride,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(2))
-        assert lib.acx_mcts_paths(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), n * stride, stream) == 0
-        out["acts"], out["tots"] = acts.cpu().numpy().reshape(n, stride), tots.cpu().numpy().reshape(n, stride)
-    return out
+    logs = torch.tensor([-math.inf] + [math.log(k) for k in range(1, 64 * (MCTS.bound(max(budgets)) + 1) + 2)],
+                        dtype=torch.float64, device=DEV)
+    return drive(lib, h, MCTS, states, budgets, L, Y.model_t(scorer),
+                 make=(logs.data_ptr(), n_log or logs.numel(), c), short_take_at=short_backup_at)
 
 
 def _check_search(out, i, y):
     _refusals_check_search(out, i, y, ("status", "nodes", "iterations"))
-
-
-def _refused(out, i, status):
-    assert out["status"][i] == status and (out["acts"][i] == SENTINEL).all() and (out["tots"][i] == SENTINEL).all(), i
-    assert (out["nodes"][i], out["iterations"][i], out["min_length"][i], out["path_len"][i]) == (0, 0, 0, 0), i
 
 
 @pytest.mark.parametrize("L", [13, 36])
@@ -518,12 +455,6 @@ def test_refused_searches_through_the_c_abi(L):
         assert lib.acx_mcts_select(h, logs.data_ptr(), 1, 1.41, pair.data_ptr(), stream) == _lib.E_ARG
     finally:
         lib.acx_mcts_destroy(h)
-
-
-def _thirteen():
-    _, valid = _rows(13)
-    rng = np.random.default_rng(77)
-    return np.concatenate([valid, np.stack([_scrambled(13, rng, 7 + i) for i in range(3)])])
 
 
 def test_a_backup_with_the_wrong_m_ends_the_search_it_cannot_serve():

@@ -15,21 +15,13 @@ import torch
 import beam_yardstick as BY
 import vgreedy_yardstick as Y
 from many_common import AK2, _dataset_rows, _load, _norm, _same, _scrambled
-from test_gpu_batch_refusals import SENTINEL, _rows
+from scored_common import AK3, Engine, _FnModel, _key, _pad, _refused, _solvable, _thirteen, drive
 from test_gpu_batch_refusals import _check_search as _refusals_check_search
+from test_gpu_batch_refusals import _rows
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-AK3 = [1, 1, 1, -2, -2, -2, -2, 1, 2, 1, -2, -1, -2]
-
-
-def _pad(letters, L, n0=7):
-    s = np.zeros(2 * L, np.int32)
-    s[:n0], s[L:L + len(letters) - n0] = letters[:n0], letters[n0:]
-    return s
-
-
 def _fn(scorer):
     if not isinstance(scorer, str):
         return scorer, {}
@@ -81,15 +73,6 @@ def test_every_fixture_record_grouped_into_single_calls(capsys):
     assert capsys.readouterr().out == ""  # value_guided_greedy_search_many prints nothing
 
 
-class _FnModel(torch.nn.Module):
-    def __init__(self, fn):
-        super().__init__()
-        self.fn = fn
-
-    def forward(self, x):
-        return self.fn(x)[:, None]
-
-
 @pytest.mark.parametrize("group", ["ak", "len", "roots raise", "ms", "norm", "long"])
 def test_fixture_records_through_value_guided_greedy_search(group):
     """the reference's signature, the model's output through expm1 on the GPU: expm1 is strictly
@@ -123,10 +106,6 @@ def test_fixture_records_through_value_guided_greedy_search(group):
 @functools.lru_cache(maxsize=None)
 def _yard(key, scorer, budget, cyc=False):
     return Y.vgreedy(np.frombuffer(key, np.int32), scorer, budget, cyc, drop_twins=True)
-
-
-def _key(p):
-    return np.ascontiguousarray(p, np.int32).tobytes()
 
 
 def _against_yardstick(pres, scorer, budgets, cyc=False, **kw):
@@ -236,11 +215,6 @@ def test_more_searches_than_resident_workgroups():
         assert res[i] == res[j] and all(st[k][i] == st[k][j] for k in st), i
     for j in range(len(rows)):
         _check_yardstick(res, st, j, _yard(_key(rows[j]), "S0", 100), j)
-
-
-def _solvable():
-    recs = [c for c in _load("greedy_many.json")["solvable"] if not c["cyclical"]][:40]
-    return np.array([c["presentation"] for c in recs]), [200 + 20 * (i % 7) for i in range(len(recs))]
 
 
 def test_split_call_equals_unsplit_call():
@@ -382,43 +356,12 @@ def test_table_scorer_over_the_float_line_against_yardstick(case):
 # ---------------------------------------------------------------------------------------------
 # the C-ABI: refusal statuses, and the calls of a step one by one
 # ---------------------------------------------------------------------------------------------
+VGREEDY = Engine("acx_vgreedy", "pop", "push", lambda cap: cap + 13)
+
+
 def _drive(lib, h, states, budgets, L, scorer="S0", short_push_at=None):
     """short_push_at: the step (0-based) whose push is told M - 1 instead of M"""
-    from acx import _lib, ops
-    n, kw = len(states), _lib.key_words(L)
-    stream = torch.cuda.current_stream(DEV).cuda_stream
-    fn = Y.SCORERS[scorer][1]
-    with torch.cuda.device(DEV):
-        st = torch.from_numpy(np.ascontiguousarray(states, np.int32)).to(DEV)
-        bd = torch.tensor(budgets, dtype=torch.int64, device=DEV)
-        pair = torch.zeros(2, dtype=torch.int64, device=DEV)
-        assert lib.acx_vgreedy_begin(h, st.data_ptr(), bd.data_ptr(), n, stream) == 0
-        for step in range(max(budgets) + 13):
-            assert lib.acx_vgreedy_pop(h, pair.data_ptr(), stream) == 0
-            M, live = pair.tolist()
-            if live == 0:
-                assert M == 0
-                break
-            if M == 0:
-                continue
-            keys = torch.empty((M, kw), dtype=torch.int64, device=DEV)
-            assert lib.acx_vgreedy_gather(h, keys.data_ptr(), M, stream) == 0
-            y = fn(ops.features(keys=keys, L=L)).to(torch.float32).contiguous()
-            assert lib.acx_vgreedy_push(h, y.data_ptr(), M - (step == short_push_at), stream) == 0
-        else:
-            raise AssertionError("the searches did not end")
-        status, min_len = (torch.full((n,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(2))
-        nodes, steps, plen = (torch.full((n,), SENTINEL, dtype=torch.int64, device=DEV) for _ in range(3))
-        assert lib.acx_vgreedy_finish(h, status.data_ptr(), nodes.data_ptr(), steps.data_ptr(), min_len.data_ptr(),
-                                      plen.data_ptr(), stream) == 0
-        out = dict(status=status.cpu().numpy(), nodes=nodes.cpu().numpy(), steps=steps.cpu().numpy(),
-                   min_length=min_len.cpu().numpy(), path_len=plen.cpu().numpy())
-        stride = int(out["path_len"].max()) + 3
-        offsets = torch.arange(n, dtype=torch.int64, device=DEV) * stride
-        acts, tots = (torch.full((n * stride,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(2))
-        assert lib.acx_vgreedy_paths(h, n, offsets.data_ptr(), acts.data_ptr(), tots.data_ptr(), n * stride, stream) == 0
-        out["acts"], out["tots"] = acts.cpu().numpy().reshape(n, stride), tots.cpu().numpy().reshape(n, stride)
-    return out
+    return drive(lib, h, VGREEDY, states, budgets, L, Y.SCORERS[scorer][1], short_take_at=short_push_at)
 
 
 def _check_search(out, i, y):
@@ -443,8 +386,7 @@ def test_refused_searches_through_the_c_abi(L):
         want = [0, _lib.MBFS_DOMAIN, _lib.MBFS_DOMAIN, _lib.MBFS_DOMAIN, _lib.MBFS_DOMAIN, _lib.MBFS_OVERFLOW, 0]
         for i, w in enumerate(want):
             if w < 0:
-                assert out["status"][i] == w and (out["acts"][i] == SENTINEL).all(), i
-                assert (out["nodes"][i], out["steps"][i], out["min_length"][i], out["path_len"][i]) == (0, 0, 0, 0), i
+                _refused(out, i, w)
             else:
                 _check_search(out, i, Y.vgreedy(batch[i], "S0", budgets[i], drop_twins=True))
         # the epoch: the same handle, seven valid rows -- a refused search left nothing behind
@@ -464,9 +406,7 @@ def test_a_push_with_the_wrong_m_ends_the_search_it_cannot_serve():
     from acx import _lib
     lib = _lib.load()
     L = 13
-    _, valid = _rows(L)
-    rng = np.random.default_rng(77)
-    rows = np.concatenate([valid, np.stack([_scrambled(L, rng, 7 + i) for i in range(3)])])
+    rows = _thirteen()
     ys = [Y.vgreedy(r, "S0", 50, drop_twins=True) for r in rows]
     last = max(i for i, y in enumerate(ys) if y["cands"] and y["cands"][0] > 0)
     assert last >= 7 and sum(bool(y["cands"]) for y in ys) >= 4
@@ -477,8 +417,7 @@ def test_a_push_with_the_wrong_m_ends_the_search_it_cannot_serve():
         out = _drive(lib, h, rows, [50] * len(rows), L, short_push_at=0)
         for i, y in enumerate(ys):
             if i == last:
-                assert out["status"][i] == _lib.MBFS_OVERFLOW and (out["acts"][i] == SENTINEL).all()
-                assert (out["nodes"][i], out["steps"][i], out["min_length"][i], out["path_len"][i]) == (0, 0, 0, 0)
+                _refused(out, i, _lib.MBFS_OVERFLOW)
             else:
                 _check_search(out, i, y)
         out = _drive(lib, h, rows, [50] * len(rows), L)

@@ -7,7 +7,7 @@ compare decides), a chunk's lanes claim along that one chain, and stale entries 
 lie anywhere in it (tests/test_weak_hash_cpu.py pins those properties of the hash).  The searches
 must not change: the expected values are the reference's recorded runs (tests/golden), the
 yardsticks (tests/bfs_yardstick.py, tests/greedy_yardstick.py, tests/beam_yardstick.py,
-tests/vgreedy_yardstick.py) and the same calls made in this process through libacx.so -- never the
+tests/vgreedy_yardstick.py, tests/mcts_yardstick.py) and the same calls made in this process through libacx.so -- never the
 variant's.
 
 The variant cannot share a process with libacx.so: each test hands its calls to one fresh child
@@ -26,6 +26,7 @@ import torch
 
 import bfs_yardstick as YB
 import greedy_yardstick as YG
+import mcts_yardstick as YM
 import test_gpu_beam_many as TBM
 import test_gpu_bfs_many as TB
 import test_gpu_greedy_many as TG
@@ -171,7 +172,8 @@ def test_device_bfs(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------
-# the batched engines (csrc/acx_mbfs.hip, csrc/acx_mgreedy.hip, csrc/acx_beam.hip, csrc/acx_vgreedy.hip)
+# the batched engines (csrc/acx_mbfs.hip, csrc/acx_mgreedy.hip, csrc/acx_beam.hip, csrc/acx_vgreedy.hip,
+# csrc/acx_mcts.hip)
 # ---------------------------------------------------------------------------------------------
 def _check_many(answer, part, tag):
     """a call's answer against the yardstick's results y of its searches [(presentation, y)]"""
@@ -283,6 +285,33 @@ def test_vgreedy_many(tmp_path):
     assert len(big) >= 3
     for n, c in big:
         _report("vgreedy_many", "a search at L=18", n, c)
+
+
+def test_mcts_many(tmp_path):
+    """AK(3), an expansion with twins and Miller-Schupp rows at L = 18, at most 2,000 nodes per
+    search, on features at c = 1.41 and on token ids at c = 0: the results are the yardstick's, and
+    every large search's nodes fall in at most 8 hash classes"""
+    twin = next(p for p, _, _, _ in YV.twin_cases() if len(p) == 36)
+    rows = [TVM._pad(TVM.AK3, 18), twin] + list(_dataset_rows()[::40])
+    budgets = [1989, 600] + [1200] * (len(rows) - 2)
+    calls = [dict(op="mcts_many", pres=[r.tolist() for r in rows], scorer=s, budgets=budgets, c=c, cyc=cyc)
+             for s, c, cyc in (("M1", 1.41, False), ("TOK", 0.0, False))]
+    out, _ = _job("mcts_many", calls, tmp_path, timeout=240)
+    large = 0
+    for call, got in zip(calls, out):
+        tokens = call["scorer"] in YM.TOKEN_MODELS
+        ys = [YM.mcts(p, YM.model_np(call["scorer"]), b, call["c"], call["cyc"], on_tokens=tokens)
+              for p, b in zip(rows, budgets)]
+        assert got["res"] == [None if y["raises"] else [y["ok"], y["path"]] for y in ys], call["scorer"]
+        for k in ("status", "nodes", "iterations"):
+            assert got["st"][k] == [y[k] for y in ys], (call["scorer"], k)
+        assert got["nodes"] == [len(y["states"]) for y in ys] and max(got["nodes"]) <= BATCH_CAP
+        assert any(y["twin_expansions"] for y in ys) and sum(y["ucb_sel"] for y in ys) >= 1000
+        for n, c in zip(got["nodes"], got["classes"]):
+            if n >= 512:
+                check_classes(n, c, ("mcts_many", call["scorer"]))
+                large += 1
+    assert large >= 12
 
 
 # ---------------------------------------------------------------------------------------------

@@ -145,6 +145,17 @@ class Ops:
                                  lambda p, j: Y.vgreedy(p, c["scorer"], c["budgets"][j], c["cyc"], drop_twins=True),
                                  scorer=Y.SCORERS[c["scorer"]][1], max_nodes_to_explore=c["budgets"])
 
+    def mcts_many(self, i, c):
+        """scorer: a name of mcts_yardstick.MODELS or TOKEN_MODELS, taken as the value itself"""
+        import acx
+        import mcts_yardstick as Y
+        tokens = c["scorer"] in Y.TOKEN_MODELS
+        return self._scored_many(acx.mcts_search_many, c,
+                                 lambda p, j: Y.mcts(p, Y.model_np(c["scorer"]), c["budgets"][j], c["c"], c["cyc"],
+                                                     on_tokens=tokens),
+                                 scorer=Y.model_t(c["scorer"]), scorer_input="tokens" if tokens else "features",
+                                 max_nodes_to_explore=c["budgets"], c_explore=c["c"])
+
     def sbfs(self, i, c):
         """arena_log2_cap: on a fresh workspace whose key arena starts at 2^cap records (the
         regrowth hook of csrc/acx_sbfs.hip), which is reset whatever happens"""
