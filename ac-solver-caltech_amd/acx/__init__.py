@@ -19,8 +19,9 @@ from .search._batch_greedy import greedy_search_many
 from .search._batch_beam import beam_search, beam_search_many
 from .search._batch_vgreedy import value_guided_greedy_search, value_guided_greedy_search_many
 from .search._batch_mcts import mcts_search, mcts_search_many
+from .search._cache import SolutionCache
 from . import data  # noqa: F401
 
 __all__ = ["ACEnv", "ACEnvConfig", "VecACEnv", "ACMove", "bfs", "bfs_many", "greedy_search",
            "greedy_search_many", "beam_search", "beam_search_many", "value_guided_greedy_search",
-           "value_guided_greedy_search_many", "mcts_search", "mcts_search_many"]
+           "value_guided_greedy_search_many", "mcts_search", "mcts_search_many", "SolutionCache"]

@@ -108,6 +108,17 @@ SIGNATURES = {
     "acx_sbfs_lookup": ([_P, _I64, _P, _P], ctypes.c_int),
     "acx_sbfs_trace": ([_P, _I64, _I64, _P, _I64, _P], ctypes.c_int64),
     "acx_sbfs_node_keys": ([_P, _P, _P, _I64, _P], ctypes.c_int64),
+    # the solution cache (ac-solver-caltech_amd/csrc/acx_cache.hip)
+    "acx_cache_bytes": ([_I32, _I64], ctypes.c_int64),
+    "acx_cache_create": ([_I32, _I64], ctypes.c_void_p),
+    "acx_cache_destroy": ([_P], None),
+    "acx_cache_info": ([_P, _P, _P], ctypes.c_int),
+    "acx_cache_count": ([_P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P], ctypes.c_int),
+    "acx_cache_reserve": ([_P, _I64, _P], ctypes.c_int),
+    "acx_cache_fill": ([_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P], ctypes.c_int),
+    "acx_cache_lookup": ([_P, _P, _I64, _P, _P, _P, _P], ctypes.c_int),
+    "acx_cache_rows": ([_P, _P, _I64, _P, _P, _P], ctypes.c_int),
+    "acx_cache_entries": ([_P, _P, _I64, _P, _P], ctypes.c_int),
     # the hash seam of the search engines (csrc/acx_test_hash.h; tests only)
     "acx_internal_hash_classes": ([], ctypes.c_int32),
     "acx_internal_key_hash": ([_P, _I32], ctypes.c_uint64),
@@ -149,6 +160,11 @@ for _prefix, _make, _take, _shape, _begin, _own in _SCORED:
         f"{_prefix}_paths": ([_P, _I64, _P, _P, _P, _I64, _P], ctypes.c_int),
         f"{_prefix}_destroy": ([_P], None),
     })
+# an attached solution cache (csrc/acx_cache.h)
+BFS_CACHED = 4
+for _prefix in ("acx_beam", "acx_vgreedy", "acx_mcts"):
+    SIGNATURES[f"{_prefix}_set_cache"] = ([_P, _P], ctypes.c_int)
+    SIGNATURES[f"{_prefix}_cache_hits"] = ([_P, _I64, _P, _P, _P, _P], ctypes.c_int)
 
 _lib = None
 

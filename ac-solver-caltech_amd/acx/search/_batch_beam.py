@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
-from . import _batch_bfs, _scored
+from . import _batch_bfs, _cache, _scored
 
 _HANDLES = {}  # (device, L, cyclical) -> (handle, searches, max_nodes_each, max_width)
 MAX_WIDTH = _lib.BEAM_MAX_WIDTH
@@ -24,12 +24,13 @@ def _wclass(w):
 
 
 # (a wider handle selects in a larger LDS class: reused only within its class)
-_BEAM = _batch_bfs._Engine("beam_search_many", "acx_beam", _HANDLES, (_lib.BFS_FOUND,), NO_PATH, extra=("max_width",),
+_BEAM = _batch_bfs._Engine("beam_search_many", "acx_beam", _HANDLES, (_lib.BFS_FOUND, _lib.BFS_CACHED), NO_PATH,
+                           extra=("max_width",),
                            reuse=lambda have, want: _wclass(have[0]) == _wclass(want[0]))
 # expand writes the candidates' number M, and the searches are over when there are none; a step
 # without a verdict adds a node to a search, and a search ends at its budget: budget + 2 steps
 _STEPS = _scored._Steps(_BEAM, "expand", "select", lambda M, _: (M, M), 2,
-                        (("nodes", np.int64), ("steps", np.int64)))
+                        (("nodes", np.int64), ("steps", np.int64)), cache=True)
 
 
 def release_workspaces() -> None:
@@ -61,7 +62,7 @@ def _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore, scor
 
 def beam_search_many(presentations, scorer, beam_width=50, max_nodes_to_explore=10000,
                      cyclically_reduce_after_moves=False, scorer_input="features", feat_mean=None, feat_std=None,
-                     device=None, on_error="raise", return_stats=False, workspace_bytes=None):
+                     device=None, on_error="raise", return_stats=False, workspace_bytes=None, solution_cache=None):
     """beam_search of every row of `presentations` ((N, 2L) array, tensor or list of equal-length
     rows), all searches stepping together: a list of (True, path) | (False, []), entry i equal to the
     reference's beam_search(presentations[i], ..., beam_width_i, budget_i) wherever the scorer's
@@ -78,12 +79,22 @@ def beam_search_many(presentations, scorer, beam_width=50, max_nodes_to_explore=
     return_stats: also return a dict of (N) arrays -- status (ACX_BFS_* of include/acx.h;
       ACX_BFS_EXHAUSTED: a step had no candidate), nodes (the reference's nodes_explored), steps.
     workspace_bytes: the most device memory the searches' workspace may take (default: half of the
-      free device memory); a larger batch runs as consecutive groups, each with its own steps."""
+      free device memory); a larger batch runs as consecutive groups, each with its own steps.
+    solution_cache: an acx.SolutionCache (or the reference's dict, uploaded for this call and never
+      mutated; pass a SolutionCache to avoid the re-upload).  The root is checked before anything,
+      and in every step each child in sequential order, after its trivial test and before its
+      visited test, as itself and with either relator rotated (value_guided_search.py:460-464,
+      503-511): a hit ends the search with (True, path to that state + the rotation moves + the
+      cached path), status ACX_BFS_CACHED and nodes = total_nodes as counted up to that child (1
+      and 0 steps for a root hit); a child beyond the step's budget cut is never looked at.  Every
+      search of the batch sees the cache as it was when the call began (acx.SolutionCache).  With
+      return_stats the dict gains cache_hit, an (N) bool array."""
     states, budgets, widths, mean, std = _validate_beam(presentations, scorer, beam_width, max_nodes_to_explore,
                                                         scorer_input, feat_mean, feat_std, on_error)
+    _cache.check(solution_cache, states.shape[1] // 2)
     return _scored._run(_STEPS, states, budgets, (widths,), (int(widths.max()),) if len(widths) else (), scorer,
                         scorer_input, mean, std, cyclically_reduce_after_moves, device, workspace_bytes, on_error,
-                        return_stats)
+                        return_stats, solution_cache=solution_cache)
 
 
 def beam_search(presentation, model, architecture="mlp", feat_mean=None, feat_std=None, beam_width=50,
@@ -98,9 +109,15 @@ def beam_search(presentation, model, architecture="mlp", feat_mean=None, feat_st
     near-tie resolved the other way changes the beam.  Everything else -- expansion order, the
     visited set, the budget cut, the stable selection -- is exact.
 
-    solution_cache and time_limit are accepted only as None; verbose prints nothing."""
+    solution_cache: an acx.SolutionCache (the reference's dict is refused with NotImplementedError:
+    upload it once with acx.SolutionCache.from_dict, or hand it to the batch call, which uploads it
+    for that call); on a hit the stats also hold 'cache_hit': True, as the reference's.  time_limit
+    is accepted only as None; verbose prints nothing."""
     solved, path, st = _scored._single(
         "beam_search", beam_search_many, presentation, model, architecture, feat_mean, feat_std, solution_cache,
         time_limit, dict(beam_width=beam_width, max_nodes_to_explore=max_nodes_to_explore),
         cyclically_reduce_after_moves=cyclically_reduce_after_moves, device=device)
-    return solved, path, {"nodes_explored": st["nodes"], "steps": st["steps"]}
+    stats = {"nodes_explored": st["nodes"], "steps": st["steps"]}
+    if st.get("cache_hit"):
+        stats["cache_hit"] = True
+    return solved, path, stats

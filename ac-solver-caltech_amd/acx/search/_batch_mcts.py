@@ -15,12 +15,12 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import _batch_bfs, _scored
+from . import _batch_bfs, _cache, _scored
 
 _HANDLES = {}  # (device, L, cyclical) -> (handle, searches, max_nodes_each)
 NO_PATH = (False, [])
 
-_MCTS = _batch_bfs._Engine("mcts_search_many", "acx_mcts", _HANDLES, (_lib.BFS_FOUND,), NO_PATH)
+_MCTS = _batch_bfs._Engine("mcts_search_many", "acx_mcts", _HANDLES, (_lib.BFS_FOUND, _lib.BFS_CACHED), NO_PATH)
 
 # log_table[k] = math.log(k) (k >= 1; entry 0 is never read), per device: (host list, device tensor).
 # It grows in chunks.  A launch runs at most MCTS_SPIN iterations of a search, and an iteration adds
@@ -48,7 +48,7 @@ def _select_args(dev, step, c_explore):
 # select writes (M, live); M == 0 with live searches: launches of dead ends.  A launch gives a search
 # at least one new node, its ending, or MCTS_SPIN of its at most 50 * budget iterations
 _STEPS = _scored._Steps(_MCTS, "select", "backup", lambda M, live: (M, live), lambda cap: cap + 50 * cap // 64 + 3,
-                        (("nodes", np.int64), ("iterations", np.int64)), make_args=_select_args)
+                        (("nodes", np.int64), ("iterations", np.int64)), make_args=_select_args, cache=True)
 
 
 def release_workspaces() -> None:
@@ -59,7 +59,7 @@ def release_workspaces() -> None:
 
 def mcts_search_many(presentations, scorer, max_nodes_to_explore=10000, c_explore=1.41,
                      cyclically_reduce_after_moves=False, scorer_input="features", feat_mean=None, feat_std=None,
-                     device=None, on_error="raise", return_stats=False, workspace_bytes=None):
+                     device=None, on_error="raise", return_stats=False, workspace_bytes=None, solution_cache=None):
     """mcts_search of every row of `presentations` ((N, 2L) array, tensor or list of equal-length
     rows), all searches stepping together: a list of (True, path) | (False, []), entry i equal to the
     reference's mcts_search(presentations[i], ..., budget_i) wherever the scorer's values equal the
@@ -82,9 +82,18 @@ def mcts_search_many(presentations, scorer, max_nodes_to_explore=10000, c_explor
       ACX_BFS_BUDGET: the budget was reached, ACX_BFS_EXHAUSTED: 50 * budget iterations were),
       nodes (the reference's nodes_explored), iterations.
     workspace_bytes: the most device memory the searches' workspace may take (default: half of the
-      free device memory); a larger batch runs as consecutive groups, each with its own steps."""
+      free device memory); a larger batch runs as consecutive groups, each with its own steps.
+    solution_cache: an acx.SolutionCache (or the reference's dict, uploaded for this call and never
+      mutated; pass a SolutionCache to avoid the re-upload).  The root is checked before the first
+      iteration, and after every expansion its new children in action order, the terminal test
+      first (mcts.py:224-229, 265-289): a hit ends the search with (True, path to that state + the
+      rotation moves + the cached path), status ACX_BFS_CACHED, and nodes counting all of that
+      expansion's new children (1 and 0 iterations for a root hit).  Every search of the batch
+      sees the cache as it was when the call began (acx.SolutionCache).  With return_stats the
+      dict gains cache_hit, an (N) bool array."""
     states, budgets = _scored._validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error,
                                                _MCTS.name)
+    _cache.check(solution_cache, states.shape[1] // 2)
     mean, std = _scored._validate_norm(scorer_input, feat_mean, feat_std)
     try:
         c = float(c_explore)
@@ -93,7 +102,8 @@ def mcts_search_many(presentations, scorer, max_nodes_to_explore=10000, c_explor
     if math.isnan(c):
         raise ValueError("c_explore must not be a NaN")
     return _scored._run(_STEPS, states, budgets, (), (), scorer, scorer_input, mean, std,
-                        cyclically_reduce_after_moves, device, workspace_bytes, on_error, return_stats, margs=c)
+                        cyclically_reduce_after_moves, device, workspace_bytes, on_error, return_stats, margs=c,
+                        solution_cache=solution_cache)
 
 
 def mcts_search(presentation, model, architecture="mlp", feat_mean=None, feat_std=None, max_nodes_to_explore=10000,
@@ -107,9 +117,15 @@ def mcts_search(presentation, model, architecture="mlp", feat_mean=None, feat_st
     two sides' values lead to the same selections; the tree, the visited set and both loop tests
     are exact.  The root is not scored.
 
-    solution_cache and time_limit are accepted only as None; verbose prints nothing."""
+    solution_cache: an acx.SolutionCache (the reference's dict is refused with NotImplementedError:
+    upload it once with acx.SolutionCache.from_dict, or hand it to the batch call, which uploads it
+    for that call); on a hit the stats also hold 'cache_hit': True, as the reference's.  time_limit is accepted only as None; verbose prints
+    nothing."""
     solved, path, st = _scored._single(
         "mcts_search", mcts_search_many, presentation, model, architecture, feat_mean, feat_std, solution_cache,
         time_limit, dict(max_nodes_to_explore=max_nodes_to_explore), no_model="a model is needed",
         c_explore=c_explore, cyclically_reduce_after_moves=cyclically_reduce_after_moves, device=device)
-    return solved, path, {"nodes_explored": st["nodes"], "iterations": st["iterations"]}
+    stats = {"nodes_explored": st["nodes"], "iterations": st["iterations"]}
+    if st.get("cache_hit"):
+        stats["cache_hit"] = True
+    return solved, path, stats

@@ -12,16 +12,17 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
-from . import _batch_bfs, _scored
+from . import _batch_bfs, _cache, _scored
 
 _HANDLES = {}  # (device, L, cyclical) -> (handle, searches, max_nodes_each)
 NO_PATH = (False, [])
 
-_VGREEDY = _batch_bfs._Engine("value_guided_greedy_search_many", "acx_vgreedy", _HANDLES, (_lib.BFS_FOUND,), NO_PATH)
+_VGREEDY = _batch_bfs._Engine("value_guided_greedy_search_many", "acx_vgreedy", _HANDLES,
+                              (_lib.BFS_FOUND, _lib.BFS_CACHED), NO_PATH)
 # pop writes (M, live); M == 0 with live searches: pops whose children were all known.  A pop takes
 # one of a search's at most budget + 11 nodes off its heap: budget + 13 steps
 _STEPS = _scored._Steps(_VGREEDY, "pop", "push", lambda M, live: (M, live), 13,
-                        (("nodes", np.int64), ("steps", np.int64), ("min_length", np.int32)))
+                        (("nodes", np.int64), ("steps", np.int64), ("min_length", np.int32)), cache=True)
 
 
 def release_workspaces() -> None:
@@ -32,7 +33,7 @@ def release_workspaces() -> None:
 def value_guided_greedy_search_many(presentations, scorer, max_nodes_to_explore=10000,
                                     cyclically_reduce_after_moves=False, scorer_input="features", feat_mean=None,
                                     feat_std=None, device=None, on_error="raise", return_stats=False,
-                                    workspace_bytes=None):
+                                    workspace_bytes=None, solution_cache=None):
     """value_guided_greedy_search of every row of `presentations` ((N, 2L) array, tensor or list of
     equal-length rows), all searches stepping together: a list of (True, path) | (False, []), entry i
     equal to the reference's value_guided_greedy_search(presentations[i], ..., budget_i) wherever the
@@ -55,12 +56,23 @@ def value_guided_greedy_search_many(presentations, scorer, max_nodes_to_explore=
       ACX_BFS_EXHAUSTED: the heap ran empty), nodes (the reference's nodes_explored), steps (pops),
       min_length.
     workspace_bytes: the most device memory the searches' workspace may take (default: half of the
-      free device memory); a larger batch runs as consecutive groups, each with its own steps."""
+      free device memory); a larger batch runs as consecutive groups, each with its own steps.
+    solution_cache: an acx.SolutionCache (or the reference's dict, uploaded for this call and never
+      mutated; pass a SolutionCache to avoid the re-upload).  The root is checked before anything,
+      and in every pop each child, after its trivial test and before its visited test, as itself
+      and with either relator rotated (value_guided_search.py:326-330, 372-380): a hit ends the
+      search with (True, path to that state + the rotation moves + the cached path), status
+      ACX_BFS_CACHED, min_length 2 and nodes as for a found search (1 for a root hit).  Every
+      search of the batch sees the cache as it was when the call began -- the reference's loop
+      backfills between two searches; here the backfill follows the call (acx.SolutionCache).
+      With return_stats the dict gains cache_hit, an (N) bool array."""
     states, budgets = _scored._validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error,
                                                _VGREEDY.name)
+    _cache.check(solution_cache, states.shape[1] // 2)
     mean, std = _scored._validate_norm(scorer_input, feat_mean, feat_std)
     return _scored._run(_STEPS, states, budgets, (), (), scorer, scorer_input, mean, std,
-                        cyclically_reduce_after_moves, device, workspace_bytes, on_error, return_stats)
+                        cyclically_reduce_after_moves, device, workspace_bytes, on_error, return_stats,
+                        solution_cache=solution_cache)
 
 
 def _total_length(f):
@@ -80,11 +92,17 @@ def value_guided_greedy_search(presentation, model=None, architecture="mlp", fea
     model the result equals the reference's only where the two sides' scores order the same; the
     expansion order, the visited set and the budget test are exact.  The root is not scored.
 
-    solution_cache and time_limit are accepted only as None; verbose prints nothing."""
+    solution_cache: an acx.SolutionCache (the reference's dict is refused with NotImplementedError:
+    upload it once with acx.SolutionCache.from_dict, or hand it to the batch call, which uploads it
+    for that call); on a hit the stats also hold 'cache_hit': True, as the reference's.  time_limit is accepted only as None; verbose prints
+    nothing."""
     solved, path, st = _scored._single(
         "value_guided_greedy_search", value_guided_greedy_search_many, presentation, model, architecture, feat_mean,
         feat_std, solution_cache, time_limit, dict(max_nodes_to_explore=max_nodes_to_explore),
         no_model="a model is needed unless use_length_priority=True",
         scorer=_total_length if use_length_priority else None,
         cyclically_reduce_after_moves=cyclically_reduce_after_moves, device=device)
-    return solved, path, {"nodes_explored": st["nodes"], "min_length": st["min_length"]}
+    stats = {"nodes_explored": st["nodes"], "min_length": st["min_length"]}
+    if st.get("cache_hit"):
+        stats["cache_hit"] = True
+    return solved, path, stats

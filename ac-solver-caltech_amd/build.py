@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "acx", "libacx.so")
 INCLUDE = os.path.join(REPO, "include")
 SOURCES = ["acx_kernels.hip", "acx_bfs.hip", "acx_mbfs.hip", "acx_mgreedy.hip", "acx_beam.hip", "acx_vgreedy.hip",
-           "acx_mcts.hip", "acx_sbfs.hip", "acx_features.hip", "acx_curriculum.hip", "acx_words.hip", "acx_greedy.hip", "acx_search.cpp"]
+           "acx_mcts.hip", "acx_cache.hip", "acx_sbfs.hip", "acx_features.hip", "acx_curriculum.hip", "acx_words.hip", "acx_greedy.hip", "acx_search.cpp"]
 # acx_kernels.hip is also compiled once per instantiation part (-DACX_PART=n, see the part table
 # and its "extern template" block in acx_launch.h), in parallel: the runtime-L generic sets took
 # ~7 minutes in one object
@@ -31,7 +31,7 @@ KERNEL_PARTS = 10
 # tests/test_gpu_weak_hash.py); nothing else does.
 WEAK_OUT = os.path.join(HERE, "acx", "libacx_weakhash.so")
 WEAK_SOURCES = ["acx_bfs.hip", "acx_mbfs.hip", "acx_mgreedy.hip", "acx_beam.hip", "acx_vgreedy.hip", "acx_mcts.hip",
-                "acx_sbfs.hip", "acx_greedy.hip", "acx_search.cpp"]
+                "acx_cache.hip", "acx_sbfs.hip", "acx_greedy.hip", "acx_search.cpp"]
 WEAK_CLASSES = 8
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ACX_OFFLOAD_ARCH", "gfx950")

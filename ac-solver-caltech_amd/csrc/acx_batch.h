@@ -233,8 +233,11 @@ struct Handle {
     int64_t n_cap = 0;
     int epoch = 0;  // the last run's epoch (0: tables all zero)
     typename E::Args a{};
+    void* cache = nullptr;       // the scored engines': an attached solution cache (acx_cache.h), not owned,
+    void* cache_hits = nullptr;  // and the attachment's hit records, one per search
 
     ~Handle() {
+        if (cache_hits) (void)hipFree(cache_hits);
         E::arrays(a, [](auto*& p, size_t, bool) {
             if (p) (void)hipFree(p);
         });

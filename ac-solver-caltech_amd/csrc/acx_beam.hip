@@ -2,8 +2,10 @@
 // owns one search, and a step of all searches is two launches with the caller's scorer between
 // them.  The searches are independent, so no workgroup ever waits on another.
 //
-// Reference: value_search/value_guided_search.py:417-561 (beam_search) with solution_cache=None
-// and time_limit=None.  The root is node 0 and total_nodes starts at 1; while total_nodes <
+// Reference: value_search/value_guided_search.py:417-561 (beam_search) with time_limit=None; the
+// solution cache is the second instantiation of the begin and expand kernels (begin_body /
+// expand_body below; beam_expand_cached_kernel<1 / 2 / 3 / 4 / 8>: 84 / 90 / 92 / 94 / 136 VGPRs,
+// profiles/cache/kernel_resources.md).  The root is node 0 and total_nodes starts at 1; while total_nodes <
 // max_nodes a step makes the beam's children in sequential order s = 12 * (rank in the beam) +
 // action, and for each in that order: a raising move ends the search (ACX_BFS_MOVE_ERROR); a child
 // of total length 2 ends it, found, before the visited test; a child not yet visited becomes the
@@ -54,6 +56,7 @@
 #include "acx.h"
 
 #include "acx_beam_key.h"
+#include "acx_cache.h"
 #include "acx_round.h"
 #include "acx_scored.h"
 
@@ -76,8 +79,17 @@ struct Args : round::Args {
     int64_t n;  // searches of the running call
 };
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* widths) {
+// The begin and expand kernels' bodies, with the solution cache's probe compiled in or not (CACHE;
+// acx_cache.h): the kernels below are their two instantiations each.  With a cache
+// (value_guided_search.py:460-464, 503-511) the root is probed before anything (a hit: nodes 1,
+// steps 0), and in a pass every child below the first raising or trivial one is probed, as the
+// reference does after a child's trivial test and before its visited test.  The first hit in
+// sequential order then stands where a trivial child would: the children before it meet the visited
+// set, a budget cut among them comes first (a cached child beyond the cut is never looked at), and
+// nodes is total_nodes as counted up to that child.  Wave w probes children w, w + 4, ... below the
+// least hit found so far.
+template <int NW, bool CACHE>
+__device__ __forceinline__ void begin_body(const Args& a, const int32_t* widths, const cache::Attach& at) {
     const int tid = threadIdx.x;
     const int64_t q = blockIdx.x;
     const int kw = a.kw;
@@ -86,6 +98,10 @@ __global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* 
     uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
     State* S = a.state + q;
     const batch::Root root = batch::root_setup<TPB, NW>(a, q, store, meta, table);
+    cache::Hit hit{cache::MISS, 0, 0};
+    if constexpr (CACHE) {
+        if (!root.refused && tid < WAVE) hit = cache::probe<NW + 1>(at.view, root.key, kw, a.L, tid);
+    }
     if (tid != 0) return;
     const int32_t w = widths[q];
     const bool wide = w < 1 || w > a.max_width;
@@ -94,10 +110,23 @@ __global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* 
     *S = State{{1, root.max_nodes, 0, 1, root.refused || wide, 0, root.total0, 0}, 1, w};
     a.beam[q * a.max_width] = 0;
     a.counts[q] = 0;
+    if constexpr (CACHE) {
+        at.hit[q] = hit;
+        if (hit.entry != cache::MISS && !wide) cache::ended_cached(a, q, S, at, hit, 0, 0, root.total0, 1, 0, 0);
+    }
 }
 
 template <int NW>
-__global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
+__global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* widths) {
+    begin_body<NW, false>(a, widths, cache::Attach{});
+}
+template <int NW>
+__global__ __launch_bounds__(TPB) void beam_begin_cached_kernel(Args a, const int32_t* widths, cache::Attach at) {
+    begin_body<NW, true>(a, widths, at);
+}
+
+template <int NW, bool CACHE>
+__device__ __forceinline__ void expand_body(const Args& a, const cache::Attach& at) {
     __shared__ Lds r;
     __shared__ uint32_t s_dec[3];    // verdict kind, children looked at, new nodes
 
@@ -127,6 +156,9 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
     const int64_t cand_base = n_nodes;
     int32_t status = 0, succ_act = 0;
     int64_t succ_node = 0;
+    bool cached = false;  // the pass's "success" child is a cache hit
+    cache::Hit hit{cache::MISS, 0, 0};
+    uint32_t hit_tot = 0;
 
     for (int base = 0; base < beam_n; base += RP) {
         const int P = beam_n - base < RP ? beam_n - base : RP;
@@ -138,6 +170,33 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
             return pn < a.rows ? pn : 0;
         });
         __syncthreads();
+        if constexpr (CACHE) {
+            __shared__ uint32_t s_hit;
+            __shared__ cache::Hit s_rec;
+            if (tid == 0) s_hit = NONE;
+            __syncthreads();
+            const uint32_t end0 = min(min(r.s_succ, r.s_err), (uint32_t)nch);
+            for (uint32_t c = (uint32_t)wid; c < end0; c += TPB / WAVE) {
+                if (c >= __hip_atomic_load(&s_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;  // (uniform in the wave)
+                const cache::Hit h = cache::probe<NW + 1>(at.view, ck + c * kw, kw, L, lane);
+                if (h.entry == cache::MISS) continue;
+                if (lane == 0) atomicMin(&s_hit, c);
+                break;  // the wave's later children come after this one
+            }
+            __syncthreads();
+            const uint32_t first = s_hit;
+            cached = first != NONE;
+            if (cached) {  // (uniform) the winner's wave probes it once more and keeps the record
+                if (wid == (int)(first % (TPB / WAVE))) {
+                    const cache::Hit h = cache::probe<NW + 1>(at.view, ck + first * kw, kw, L, lane);
+                    if (lane == 0) s_rec = h;
+                }
+                if (tid == 0) r.s_succ = first;  // it stands where a trivial child would
+                __syncthreads();
+                hit = s_rec;
+                hit_tot = r.ctot[first];
+            }
+        }
         insert<NW>(r, ck, store, table, a, n_nodes, nch, kw);
         __syncthreads();
         if (r.s_over) {  // (uniform) cannot happen at load <= 1/2
@@ -203,6 +262,7 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
         __syncthreads();
         running = min(running, r.s_min);
         n_nodes += newn;
+        if (kind != ACX_BFS_FOUND) cached = false;  // a budget cut came first: the hit is never looked at
         if (kind == ACX_BFS_FOUND || kind == ACX_BFS_MOVE_ERROR) {
             status = (int32_t)kind;
             if (kind == ACX_BFS_FOUND) {
@@ -219,7 +279,10 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
     if (status != 0) {
         // the edges to the success child's parent + (action, 2)
         const int64_t plen = status == ACX_BFS_FOUND ? batch::path_depth(meta, succ_node, a.rows) + 1 : 0;
-        ended(a, q, S, status, succ_act, succ_node, n_nodes, steps, running, plen);
+        if (CACHE && cached && status == ACX_BFS_FOUND)
+            cache::ended_cached(a, q, S, at, hit, succ_act, succ_node, hit_tot, n_nodes, steps, plen);
+        else
+            ended(a, q, S, status, succ_act, succ_node, n_nodes, steps, running, plen);
     } else if (cand_n == 0) {  // the beam died
         ended(a, q, S, ACX_BFS_EXHAUSTED, 0, 0, n_nodes, steps, running, 0);
     } else {
@@ -230,6 +293,15 @@ __global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
         S->running = running;
         a.counts[q] = (int32_t)cand_n;
     }
+}
+
+template <int NW>
+__global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
+    expand_body<NW, false>(a, cache::Attach{});
+}
+template <int NW>
+__global__ __launch_bounds__(TPB) void beam_expand_cached_kernel(Args a, cache::Attach at) {
+    expand_body<NW, true>(a, at);
 }
 
 template <int CAP, int THREADS>
@@ -285,7 +357,8 @@ __global__ __launch_bounds__(THREADS) void beam_select_kernel(Args a, const floa
 struct Engine {
     using Args = beam::Args;
     // a found search's path (value_guided_search.py:87-97,497-498): the edges + (action, 2), no root entry
-    static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND;
+    // a search that ended on a cache hit below the root: the edges + the (action, total) of the child that hit
+    static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND | 1u << ACX_BFS_CACHED;
     static constexpr bool ROOT_ENTRY = false;
     static constexpr int GATHER_THREADS = TPB, MOST = 0;
     static constexpr bool LIVE = false;
@@ -319,6 +392,21 @@ struct Expand {
     template <int NW>
     void go() { beam_expand_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a); }
 };
+struct BeginCached {
+    const Args& a;
+    hipStream_t st;
+    const int32_t* widths;
+    cache::Attach at;
+    template <int NW>
+    void go() { beam_begin_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a, widths, at); }
+};
+struct ExpandCached {
+    const Args& a;
+    hipStream_t st;
+    cache::Attach at;
+    template <int NW>
+    void go() { beam_expand_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a, at); }
+};
 
 }  // namespace beam
 }  // namespace acx
@@ -344,10 +432,22 @@ void acx_beam_destroy(void* h) { batch::destroy<beam::Engine>(h); }
 
 int acx_beam_begin(void* h, const int32_t* states, const int64_t* budgets, const int32_t* widths, int64_t n,
                    void* stream) {
+    acx::cache::Attach at;
+    if (h && acx::cache::attached(static_cast<batch::Handle<beam::Engine>*>(h), at))
+        return scored::begin<beam::Engine, beam::BeginCached>(h, states, budgets, widths != nullptr, n, stream, widths, at);
     return scored::begin<beam::Engine, beam::Begin>(h, states, budgets, widths != nullptr, n, stream, widths);
 }
 
+int acx_beam_set_cache(void* h, void* cache) { return acx::cache::set_cache<batch::Handle<beam::Engine>>(h, cache); }
+
+int acx_beam_cache_hits(void* h, int64_t n, int64_t* entry, int32_t* rel, int32_t* k, void* stream) {
+    return acx::cache::read_hits<batch::Handle<beam::Engine>>(h, n, entry, rel, k, stream);
+}
+
 int acx_beam_expand(void* h, int64_t* total, void* stream) {
+    acx::cache::Attach at;
+    if (h && acx::cache::attached(static_cast<batch::Handle<beam::Engine>*>(h), at))
+        return scored::make<beam::Engine, beam::ExpandCached>(h, total, stream, at);
     return scored::make<beam::Engine, beam::Expand>(h, total, stream);
 }
 

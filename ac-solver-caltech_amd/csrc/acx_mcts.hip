@@ -4,8 +4,8 @@
 // the third engine of the scored-step frame (acx_scored.h): where acx_vgreedy.hip has a heap, this
 // one has a tree with visit statistics, UCB1 selection and a backup.
 //
-// Reference: value_search/mcts.py:177-314 (mcts_search) with solution_cache=None and
-// time_limit=None.  The root is node 0 with visit = 1; its own value is never read, so it is not
+// Reference: value_search/mcts.py:177-314 (mcts_search) with time_limit=None; the solution cache
+// is the second instantiation of the begin and select kernels (begin_body / select_body below).  The root is node 0 with visit = 1; its own value is never read, so it is not
 // scored.  At the top of every iteration: len(visited) < budget and iterations < 50 * budget
 // (:244), so a budget of 0 or 1 runs no iteration, and an iteration overshoots the budget by up to
 // 11 nodes.  An iteration:
@@ -84,6 +84,7 @@
 #include "acx_batch.h"
 #include "acx_beam_key.h"
 #include "acx_bfs_common.h"
+#include "acx_cache.h"
 #include "acx_pop.h"
 #include "acx_scored.h"
 #include "acx_visited.h"
@@ -155,13 +156,22 @@ __device__ __forceinline__ void back_up(Rec* rec, const uint32_t* trail, int tl,
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(GT) void mcts_begin_kernel(Args a) {
+// The begin and select kernels' bodies, with the solution cache's probe compiled in or not (CACHE;
+// acx_cache.h): the kernels below are their two instantiations each.  With a cache
+// (mcts.py:224-229, 265-289) the root is probed before the first iteration, and after an expansion
+// its new children -- not the ones already visited -- are looked at in action order, the terminal
+// test first, then the cache; nodes_explored counts all of the expansion's new children.
+template <int NW, bool CACHE>
+__device__ __forceinline__ void begin_body(const Args& a, const cache::Attach& at) {
     const int64_t q = blockIdx.x;
     uint64_t* store = a.store + q * a.rows * a.kw;
     uint32_t* meta = a.meta + q * a.rows;
     uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
     const batch::Root root = batch::root_setup<GT, NW>(a, q, store, meta, table);
+    cache::Hit hit{cache::MISS, 0, 0};
+    if constexpr (CACHE) {
+        if (!root.refused) hit = cache::probe<NW + 1>(at.view, root.key, a.kw, a.L, threadIdx.x);
+    }
     if (threadIdx.x != 0) return;
     // (a search's results are written where it ends)
     if (!root.refused) batch::write_result(a, q, Res{ACX_MBFS_OVERFLOW, 0, 0, 0, 0, 0}, 0, 0, 0);
@@ -169,10 +179,24 @@ __global__ __launch_bounds__(GT) void mcts_begin_kernel(Args a) {
     (a.depth + q * a.rows)[0] = 0;
     (a.rec + q * a.rows)[0] = Rec{0.0, 1u, 0.0f, 0u, 0u};  // visit = 1 (mcts.py:234); the value is never read
     a.counts[q] = 0;
+    if constexpr (CACHE) {
+        at.hit[q] = hit;
+        if (hit.entry != cache::MISS) cache::ended_cached(a, q, a.state + q, at, hit, 0, 0, root.total0, 1, 0, 0);
+    }
 }
 
 template <int NW>
-__global__ __launch_bounds__(GT) void mcts_select_kernel(Args a, const double* log_table, int64_t n_log, double c) {
+__global__ __launch_bounds__(GT) void mcts_begin_kernel(Args a) {
+    begin_body<NW, false>(a, cache::Attach{});
+}
+template <int NW>
+__global__ __launch_bounds__(GT) void mcts_begin_cached_kernel(Args a, cache::Attach at) {
+    begin_body<NW, true>(a, at);
+}
+
+template <int NW, bool CACHE>
+__device__ __forceinline__ void select_body(const Args& a, const double* log_table, int64_t n_log, double c,
+                                            const cache::Attach& at) {
     __shared__ uint64_t ck[12 * (NW + 1)];  // the expansion's child keys, kw words each
     __shared__ uint32_t slot[12];           // table index of the entry a child holds
     __shared__ uint32_t lost[12];           // an earlier child of the expansion took that entry
@@ -317,6 +341,18 @@ __global__ __launch_bounds__(GT) void mcts_select_kernel(Args a, const double* l
         const int64_t base = n_nodes;
         n_nodes += cnt;
         const uint32_t trivial = (uint32_t)__ballot(alive && ch.tot == 2u);
+        if constexpr (CACHE) {  // the new children below the first trivial one, in action order
+            const uint32_t upto = trivial ? (uint32_t)__builtin_ctz(trivial) : 12u;
+            for (uint32_t cc = 0; cc < upto; ++cc) {
+                if (!((sv.m >> cc) & 1u)) continue;
+                const cache::Hit hit = cache::probe<NW + 1>(at.view, ck + cc * kw, kw, L, lane);
+                if (hit.entry == cache::MISS) continue;
+                if (lane == 0)
+                    cache::ended_cached(a, q, S, at, hit, (int32_t)cc, leaf, (uint32_t)key_total(ck + cc * kw, L), n_nodes,
+                                        iters, (int64_t)dpar + 1);
+                return;
+            }
+        }
         if (trivial) {  // the first trivial new child (:267-270)
             if (lane == 0)
                 ended(a, q, S, ACX_BFS_FOUND, __builtin_ctz(trivial), leaf, n_nodes, iters, running, (int64_t)dpar + 1);
@@ -347,6 +383,16 @@ __global__ __launch_bounds__(GT) void mcts_select_kernel(Args a, const double* l
         S->steps = iters;
         a.counts[q] = 0;
     }
+}
+
+template <int NW>
+__global__ __launch_bounds__(GT) void mcts_select_kernel(Args a, const double* log_table, int64_t n_log, double c) {
+    select_body<NW, false>(a, log_table, n_log, c, cache::Attach{});
+}
+template <int NW>
+__global__ __launch_bounds__(GT) void mcts_select_cached_kernel(Args a, const double* log_table, int64_t n_log, double c,
+                                                                cache::Attach at) {
+    select_body<NW, true>(a, log_table, n_log, c, at);
 }
 
 __global__ __launch_bounds__(GT) void mcts_backup_kernel(Args a, const float* scores, int64_t M) {
@@ -406,7 +452,8 @@ __global__ __launch_bounds__(TPB) void ucb_kernel(const double* vsum, const uint
 struct Engine {
     using Args = mcts::Args;
     // a found search's path (mcts.py:166-174): the edges to the trivial child, no root entry
-    static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND;
+    // a search that ended on a cache hit below the root: the edges to the child that hit
+    static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND | 1u << ACX_BFS_CACHED;
     static constexpr bool ROOT_ENTRY = false;
     static constexpr int GATHER_THREADS = GT, MOST = 12;
     static constexpr bool LIVE = true;
@@ -435,6 +482,23 @@ struct Select {
     template <int NW>
     void go() { mcts_select_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, log_table, n_log, c); }
 };
+struct BeginCached {
+    const Args& a;
+    hipStream_t st;
+    cache::Attach at;
+    template <int NW>
+    void go() { mcts_begin_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at); }
+};
+struct SelectCached {
+    const Args& a;
+    hipStream_t st;
+    const double* log_table;
+    int64_t n_log;
+    double c;
+    cache::Attach at;
+    template <int NW>
+    void go() { mcts_select_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, log_table, n_log, c, at); }
+};
 
 }  // namespace mcts
 }  // namespace acx
@@ -455,11 +519,23 @@ void* acx_mcts_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int
 void acx_mcts_destroy(void* h) { batch::destroy<Engine>(h); }
 
 int acx_mcts_begin(void* h, const int32_t* states, const int64_t* budgets, int64_t n, void* stream) {
+    acx::cache::Attach at;
+    if (h && acx::cache::attached(static_cast<batch::Handle<Engine>*>(h), at))
+        return scored::begin<Engine, mcts::BeginCached>(h, states, budgets, true, n, stream, at);
     return scored::begin<Engine, mcts::Begin>(h, states, budgets, true, n, stream);
+}
+
+int acx_mcts_set_cache(void* h, void* cache) { return acx::cache::set_cache<batch::Handle<Engine>>(h, cache); }
+
+int acx_mcts_cache_hits(void* h, int64_t n, int64_t* entry, int32_t* rel, int32_t* k, void* stream) {
+    return acx::cache::read_hits<batch::Handle<Engine>>(h, n, entry, rel, k, stream);
 }
 
 int acx_mcts_select(void* h, const double* log_table, int64_t n_log, double c_explore, int64_t* pair, void* stream) {
     if (!log_table || n_log < 2 || c_explore != c_explore) return ACX_E_ARG;
+    acx::cache::Attach at;
+    if (h && acx::cache::attached(static_cast<batch::Handle<Engine>*>(h), at))
+        return scored::make<Engine, mcts::SelectCached>(h, pair, stream, log_table, n_log, c_explore, at);
     return scored::make<Engine, mcts::Select>(h, pair, stream, log_table, n_log, c_explore);
 }
 

@@ -5,7 +5,8 @@
 // launch after the nodes they belong to.
 //
 // Reference: value_search/value_guided_search.py:294-414 (value_guided_greedy_search) with
-// solution_cache=None and time_limit=None.  The root is node 0 and the only heap entry; its score
+// time_limit=None; the solution cache is the second instantiation of the begin and pop kernels
+// (acx_cache.h; below, "with a cache").  The root is node 0 and the only heap entry; its score
 // never decides anything, so it is not scored.  While the heap is not empty the least (score,
 // path_length, node_id) is popped -- node ids are unique, so the order is total and no state is
 // ever compared (unlike acx_prio.h) -- and its 12 children are taken in action order; per child: a
@@ -67,6 +68,15 @@
 //       106 SGPRs with 92 / 96 / 117 / 162 / 119 SGPR spills, kept in VGPR lanes (no scratch for them);
 //   vgreedy_push_kernel 26 VGPRs, no LDS; vgreedy_begin_kernel 11 VGPRs, 96 B; the frame's offsets,
 //   gather and results kernels 53 (64 B of LDS), 8 and 13 VGPRs.
+//
+// With a cache (acx_vgreedy_set_cache; value_guided_search.py:326-330, 372-380): the root is probed
+// in the begin kernel (a hit: nodes 1, min_length 2, no pop), and a pop probes its children in
+// action order below the first raising or trivial one -- the reference tests a child's triviality,
+// then the cache, then the visited set -- one wave-wide probe per child.  A hit ends the search with
+// ACX_BFS_CACHED, the nodes of a found search and min_length 2; the path reader returns the path to
+// the popped node plus the child's (action, total), and the hit record (entry, rel, k) goes to the
+// attachment's array, not to the search's slice.  vgreedy_pop_cached_kernel<1 / 2 / 3 / 4 / 8>:
+// 53 / 55 / 57 / 59 / 68 VGPRs, the same LDS (profiles/cache/kernel_resources.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -76,6 +86,7 @@
 #include "acx_batch.h"
 #include "acx_beam_key.h"
 #include "acx_bfs_common.h"
+#include "acx_cache.h"
 #include "acx_heap.h"
 #include "acx_pop.h"
 #include "acx_scored.h"
@@ -113,13 +124,19 @@ struct Order {
     }
 };
 
-template <int NW>
-__global__ __launch_bounds__(GT) void vgreedy_begin_kernel(Args a) {
+// The begin and pop kernels' bodies, with the solution cache's probe compiled in or not (CACHE;
+// acx_cache.h): the kernels below are their two instantiations each.
+template <int NW, bool CACHE>
+__device__ __forceinline__ void begin_body(const Args& a, const cache::Attach& at) {
     const int64_t q = blockIdx.x;
     uint64_t* store = a.store + q * a.rows * a.kw;
     uint32_t* meta = a.meta + q * a.rows;
     uint64_t* table = a.table + q * (int64_t)a.nb * BUCKET;
     const batch::Root root = batch::root_setup<GT, NW>(a, q, store, meta, table);
+    cache::Hit hit{cache::MISS, 0, 0};
+    if constexpr (CACHE) {  // the root is checked before anything (value_guided_search.py:326-330)
+        if (!root.refused) hit = cache::probe<NW + 1>(at.view, root.key, a.kw, a.L, threadIdx.x);
+    }
     if (threadIdx.x != 0) return;
     // (a search's results are written where it ends)
     if (!root.refused) batch::write_result(a, q, Res{ACX_MBFS_OVERFLOW, 0, 0, 0, 0, 0}, 0, 0, 0);
@@ -128,10 +145,23 @@ __global__ __launch_bounds__(GT) void vgreedy_begin_kernel(Args a) {
     (a.hk + q * a.rows)[0] = 0;  // the root's score decides nothing: it is the only entry
     (a.hid + q * a.rows)[0] = 0;
     a.counts[q] = 0;
+    if constexpr (CACHE) {
+        at.hit[q] = hit;
+        if (hit.entry != cache::MISS) cache::ended_cached(a, q, a.state + q, at, hit, 0, 0, root.total0, 1, 0, 0);
+    }
 }
 
 template <int NW>
-__global__ __launch_bounds__(GT) void vgreedy_pop_kernel(Args a) {
+__global__ __launch_bounds__(GT) void vgreedy_begin_kernel(Args a) {
+    begin_body<NW, false>(a, cache::Attach{});
+}
+template <int NW>
+__global__ __launch_bounds__(GT) void vgreedy_begin_cached_kernel(Args a, cache::Attach at) {
+    begin_body<NW, true>(a, at);
+}
+
+template <int NW, bool CACHE>
+__device__ __forceinline__ void pop_body(const Args& a, const cache::Attach& at) {
     __shared__ uint64_t ck[12 * (NW + 1)];  // the pop's child keys, kw words each
     __shared__ uint32_t slot[12];           // table index of the entry a child holds
     __shared__ uint32_t lost[12];           // an earlier child of the pop took that entry
@@ -172,6 +202,20 @@ __global__ __launch_bounds__(GT) void vgreedy_pop_kernel(Args a) {
     const Children ch = expand<NW>(store, id, ck, lost, lane, L, kw, cyc, [](uint32_t) {});
     running = min(running, wave_min((uint32_t)lane < ch.seen_to ? ch.tot : NONE));
     __syncthreads();
+    if constexpr (CACHE) {
+        // the children the reference looks at, in action order: each is probed after its trivial test
+        // and before its visited test (:372-380), so the first hit below the first raising or trivial
+        // child ends the search; one wave-wide probe per child, at most 12
+        const uint32_t upto = min(ch.end0, 12u);
+        for (uint32_t c = 0; c < upto; ++c) {
+            const cache::Hit hit = cache::probe<NW + 1>(at.view, ck + c * kw, kw, L, lane);
+            if (hit.entry == cache::MISS) continue;
+            if (lane == 0)
+                cache::ended_cached(a, q, S, at, hit, (int32_t)c, id, (uint32_t)key_total(ck + c * kw, L), n_nodes, steps,
+                                    (int64_t)dpar + 1);
+            return;
+        }
+    }
     if (ch.end0 != NONE) {  // nodes_explored: the distinct states before this pop's children
         if (lane == 0) {
             if (ch.first_err < ch.first_suc)
@@ -228,6 +272,15 @@ __global__ __launch_bounds__(GT) void vgreedy_pop_kernel(Args a) {
     }
 }
 
+template <int NW>
+__global__ __launch_bounds__(GT) void vgreedy_pop_kernel(Args a) {
+    pop_body<NW, false>(a, cache::Attach{});
+}
+template <int NW>
+__global__ __launch_bounds__(GT) void vgreedy_pop_cached_kernel(Args a, cache::Attach at) {
+    pop_body<NW, true>(a, at);
+}
+
 __global__ __launch_bounds__(GT) void vgreedy_push_kernel(Args a, const float* scores, int64_t M) {
     const int lane = threadIdx.x;
     const int64_t q = blockIdx.x;
@@ -278,7 +331,8 @@ __global__ __launch_bounds__(GT) void vgreedy_push_kernel(Args a, const float* s
 struct Engine {
     using Args = vgreedy::Args;
     // a found search's path (value_guided_search.py:87-97,366-367): the edges + (action, 2), no root entry
-    static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND;
+    // a search that ended on a cache hit below the root: the edges + the (action, total) of the state that hit
+    static constexpr uint32_t WITH_PATH = 1u << ACX_BFS_FOUND | 1u << ACX_BFS_CACHED;
     static constexpr bool ROOT_ENTRY = false;
     static constexpr int GATHER_THREADS = GT, MOST = 12;
     static constexpr bool LIVE = true;
@@ -304,6 +358,20 @@ struct Pop {
     template <int NW>
     void go() { vgreedy_pop_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a); }
 };
+struct BeginCached {
+    const Args& a;
+    hipStream_t st;
+    cache::Attach at;
+    template <int NW>
+    void go() { vgreedy_begin_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at); }
+};
+struct PopCached {
+    const Args& a;
+    hipStream_t st;
+    cache::Attach at;
+    template <int NW>
+    void go() { vgreedy_pop_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at); }
+};
 
 }  // namespace vgreedy
 }  // namespace acx
@@ -324,10 +392,24 @@ void* acx_vgreedy_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, 
 void acx_vgreedy_destroy(void* h) { batch::destroy<Engine>(h); }
 
 int acx_vgreedy_begin(void* h, const int32_t* states, const int64_t* budgets, int64_t n, void* stream) {
+    acx::cache::Attach at;
+    if (h && acx::cache::attached(static_cast<batch::Handle<Engine>*>(h), at))
+        return scored::begin<Engine, vgreedy::BeginCached>(h, states, budgets, true, n, stream, at);
     return scored::begin<Engine, vgreedy::Begin>(h, states, budgets, true, n, stream);
 }
 
-int acx_vgreedy_pop(void* h, int64_t* pair, void* stream) { return scored::make<Engine, vgreedy::Pop>(h, pair, stream); }
+int acx_vgreedy_pop(void* h, int64_t* pair, void* stream) {
+    acx::cache::Attach at;
+    if (h && acx::cache::attached(static_cast<batch::Handle<Engine>*>(h), at))
+        return scored::make<Engine, vgreedy::PopCached>(h, pair, stream, at);
+    return scored::make<Engine, vgreedy::Pop>(h, pair, stream);
+}
+
+int acx_vgreedy_set_cache(void* h, void* cache) { return acx::cache::set_cache<batch::Handle<Engine>>(h, cache); }
+
+int acx_vgreedy_cache_hits(void* h, int64_t n, int64_t* entry, int32_t* rel, int32_t* k, void* stream) {
+    return acx::cache::read_hits<batch::Handle<Engine>>(h, n, entry, rel, k, stream);
+}
 
 int acx_vgreedy_gather(void* h, uint64_t* keys, int64_t M, void* stream) {
     return scored::gather<Engine>(h, keys, M, stream);

@@ -423,6 +423,7 @@ int acx_unpack_keys(const uint64_t* keys, int32_t* states, int32_t* lengths_out,
 #define ACX_BFS_FOUND 1      /* (True, path) */
 #define ACX_BFS_BUDGET 2     /* len(tree_nodes) >= max_nodes after a parent: (False, None) */
 #define ACX_BFS_MOVE_ERROR 3 /* an ACMove raised AssertionError (a relator became empty) */
+#define ACX_BFS_CACHED 4     /* a state of an attached solution cache was reached (acx_*_set_cache): (True, path) */
 void* acx_bfs_create(int32_t L, int64_t max_nodes, int64_t chunk_parents, int32_t cyclical);
 int acx_bfs_run(void* h, const int32_t* presentation, int64_t max_nodes, int32_t* path_actions,
                 int32_t* path_totals, int64_t path_cap, int64_t* stats, void* stream);
@@ -695,6 +696,86 @@ int acx_mcts_finish(void* h, int32_t* status, int64_t* nodes, int64_t* iteration
 int acx_mcts_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actions, int32_t* totals, int64_t cap,
                    void* stream);
 void acx_mcts_destroy(void* h);
+
+/*
+ * The solution cache of value_search/value_guided_search.py:100-250 on the device (csrc/acx_cache.hip):
+ * a hash set of packed state keys for one L that outlives a call.  A row of its key store is one
+ * "if absent" test of the reference's sequential backfill, in that order, and an equal state's
+ * entry is held by the least row, so the set is the reference's dict whatever order the lanes run in.
+ *   acx_cache_bytes    device bytes at a capacity of C rows, kw = acx_key_words(L):
+ *                        (8 kw + 8) C + 64 ceil(C / 4) + 16
+ *                      (a key and a meta word per row, the table at load <= 1/2, the counters);
+ *                      ACX_E_ARG for L outside [1, ACX_MAX_L] or C outside [1, 2^33].
+ *   acx_cache_create   an empty cache on the current device; NULL on bad arguments or no memory.
+ *   acx_cache_info     synchronises; out int64[5] = distinct states held, rows used, capacity,
+ *                      buckets, 1 if an insert ever found the table full (never at load <= 1/2).
+ *   acx_cache_count    (value_guided_search.py:212-250) replays P paths: `states` DEVICE (P, 2L)
+ *                      int32, `poff` DEVICE (P + 1) int64 offsets into `actions` DEVICE int32.
+ *                      counts[p] = the rows path p would emit (every state before its last, and with
+ *                      expand_rotations every rotation variant); err[p] = 0, or 1 + the step whose
+ *                      move raises in the reference, or -1 for a row outside the packed domain.
+ *                      replay = 0: a row is one entry, its state alone (a dict's key).  Writes
+ *                      nothing to the cache.
+ *   acx_cache_reserve  grows the capacity by doubling until `rows` fit; the entries are rehashed,
+ *                      codes kept, into a table of as many times the buckets.  Synchronises.
+ *   acx_cache_fill     the same replay, emitting path p's rows at voff[p] (DEVICE (P + 1) int64, the
+ *                      exclusive prefix sum of acx_cache_count's counts, total = voff[P]) after the
+ *                      rows in use, then inserts them; path p is ordinal0 + p.  ACX_E_ARG when the
+ *                      rows do not fit the capacity (call acx_cache_reserve first).
+ *   acx_cache_lookup   (value_guided_search.py:100-153) for each of n states (DEVICE (n, 2L) int32)
+ *                      the first hit among the state, relator 0 rotated left by k = 1 .. n0 - 1 and
+ *                      relator 1 by k = 1 .. n1 - 1: entry (row; -1: none, or a row outside the
+ *                      packed domain), rel, k.
+ *   acx_cache_rows     keys (m, kw) and meta words (m) of the rows `entries` (DEVICE (m) int64):
+ *                      meta = path ordinal << 32 | step << 9 | rel << 8 | k.
+ *   acx_cache_entries  the rows that hold a state, in no order, at most cap of them into `out`;
+ *                      *n (DEVICE) counts them all.
+ *   acx_cache_destroy  frees it.
+ * Calls are asynchronous on `stream` unless they say otherwise; a cache must not be filled or grown
+ * while a search that has it attached runs.
+ */
+int64_t acx_cache_bytes(int32_t L, int64_t capacity);
+void* acx_cache_create(int32_t L, int64_t capacity);
+void acx_cache_destroy(void* h);
+int acx_cache_info(void* h, int64_t* out, void* stream);
+int acx_cache_count(void* h, const int32_t* states, const int64_t* poff, const int32_t* actions, int64_t P,
+                    int32_t cyclical, int32_t expand_rotations, int32_t replay, int64_t* counts, int32_t* err,
+                    void* stream);
+int acx_cache_reserve(void* h, int64_t rows, void* stream);
+int acx_cache_fill(void* h, const int32_t* states, const int64_t* poff, const int32_t* actions, const int64_t* voff,
+                   int64_t total, int64_t ordinal0, int64_t P, int32_t cyclical, int32_t expand_rotations,
+                   int32_t replay, void* stream);
+int acx_cache_lookup(void* h, const int32_t* states, int64_t n, int64_t* entry, int32_t* rel, int32_t* k,
+                     void* stream);
+int acx_cache_rows(void* h, const int64_t* entries, int64_t m, uint64_t* keys, uint64_t* metas, void* stream);
+int acx_cache_entries(void* h, int64_t* out, int64_t cap, int64_t* n, void* stream);
+
+/*
+ * A cache attached to a handle of the beam search, of the value-guided greedy search or of MCTS:
+ * the searches begun while it is attached probe their root (a hit: nodes 1, no step) and then
+ *   beam    (value_guided_search.py:460-464, 503-511)  in every step each child in sequential
+ *           order, after its trivial test and before its visited test; nodes is total_nodes as
+ *           counted up to that child, and a child beyond the step's budget cut is never looked at;
+ *   vgreedy (value_guided_search.py:326-330, 372-380)  in every pop each child in action order,
+ *           after its trivial test and before its visited test; nodes as on ACX_BFS_FOUND;
+ *   mcts    (mcts.py:224-229, 265-289)  after every expansion its new children in action order,
+ *           the terminal test first; nodes counts all of the expansion's new children.
+ * A hit ends the search with ACX_BFS_CACHED (min_length 2); acx_*_paths writes the path to the
+ * state that hit, that state's (action, total) included, and nothing for a root hit.
+ *   acx_*_set_cache   `cache`: an acx_cache_create handle of the same L, or NULL to detach.  The
+ *                     cache is read as it stands when acx_*_begin is called and must not be filled
+ *                     or grown before acx_*_finish.
+ *   acx_*_cache_hits  after acx_*_finish: per search of the last run the hit's entry (a cache row;
+ *                     -1: the search did not end on a hit), and the relator and the k by which the
+ *                     state was rotated to meet it (acx_cache_lookup).
+ * The hit records are the attachment's: acx_beam_bytes, acx_vgreedy_bytes and acx_mcts_bytes do not change.
+ */
+int acx_vgreedy_set_cache(void* h, void* cache);
+int acx_vgreedy_cache_hits(void* h, int64_t n, int64_t* entry, int32_t* rel, int32_t* k, void* stream);
+int acx_beam_set_cache(void* h, void* cache);
+int acx_beam_cache_hits(void* h, int64_t n, int64_t* entry, int32_t* rel, int32_t* k, void* stream);
+int acx_mcts_set_cache(void* h, void* cache);
+int acx_mcts_cache_hits(void* h, int64_t n, int64_t* entry, int32_t* rel, int32_t* k, void* stream);
 
 /*
  * Breadth-first search with the node store and the visited set partitioned over G GPUs by key
