@@ -7,7 +7,8 @@ are bfs and greedy_search over a batch of presentations in one launch, beam_sear
 beam_search the reference's value-guided beam search (value_search/value_guided_search.py) over a
 batch, scored by the caller's model, value_guided_greedy_search_many and value_guided_greedy_search
 its value-guided greedy search, mcts_search_many and mcts_search its MCTS (value_search/mcts.py),
-likewise.
+likewise; DeviceMLP is the reference's FeatureMLP as device code, which the value-guided greedy
+search runs fused, with no Python between the pops.
 """
 
 from .envs.ac_env import ACEnv, ACEnvConfig, VecACEnv
@@ -20,8 +21,9 @@ from .search._batch_beam import beam_search, beam_search_many
 from .search._batch_vgreedy import value_guided_greedy_search, value_guided_greedy_search_many
 from .search._batch_mcts import mcts_search, mcts_search_many
 from .search._cache import SolutionCache
+from ._mlp import DeviceMLP
 from . import data  # noqa: F401
 
 __all__ = ["ACEnv", "ACEnvConfig", "VecACEnv", "ACMove", "bfs", "bfs_many", "greedy_search",
            "greedy_search_many", "beam_search", "beam_search_many", "value_guided_greedy_search",
-           "value_guided_greedy_search_many", "mcts_search", "mcts_search_many", "SolutionCache"]
+           "value_guided_greedy_search_many", "mcts_search", "mcts_search_many", "SolutionCache", "DeviceMLP"]

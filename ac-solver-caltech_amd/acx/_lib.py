@@ -66,6 +66,10 @@ SIGNATURES = {
     "acx_version": ([], ctypes.c_char_p),
     "acx_features": ([_P] * 5 + [_I64, _I32, _P], ctypes.c_int),
     "acx_token_ids": ([_P] * 3 + [_I64, _I32, _I32, _P], ctypes.c_int),
+    # the FeatureMLP scorer (csrc/acx_mlp.hip, acx_mlp_host.cpp) and the fused pops of acx_vgreedy.hip
+    "acx_mlp_scores": ([_P, _P, _P, _I32, _P, _I64, _P], ctypes.c_int),
+    "acx_mlp_scores_host": ([_P, _P, _P, _I32, _P, _I64], ctypes.c_int),
+    "acx_vgreedy_run_mlp": ([_P, _P, _P, _I32, _P, _P, _I64, _P, _P], ctypes.c_int),
     # host-side search engine (ac-solver-caltech_amd/csrc/acx_search.cpp)
     "acx_search_create": ([_I32, _I32, _P, _I64], ctypes.c_void_p),
     "acx_search_destroy": ([_P], None),

@@ -648,6 +648,23 @@ def token_ids(*, states: Optional[torch.Tensor] = None, keys: Optional[torch.Ten
     return out
 
 
+def mlp_scores(x: torch.Tensor, mlp, expm1: bool = False, out: Optional[torch.Tensor] = None):
+    """acx_mlp_scores: an acx.DeviceMLP over (M,14) float32 device features (as the network takes
+    them: already normalised) -> (M,) float32, the last layer's output y in the arithmetic of
+    csrc/acx_mlp.h, bit for bit what mlp.host gives.  expm1=True returns torch.expm1(y), the
+    reference's score (value_guided_search.py:49-66), for callers to whom magnitudes matter (MCTS)."""
+    lib = _lib.load()
+    _need_gpu(x, "x")
+    M, dev = x.shape[0], x.device
+    _check(x, "x", torch.float32, (M, 14), dev)
+    if out is None:
+        out = torch.empty((M,), dtype=torch.float32, device=dev)
+    _check(out, "out", torch.float32, (M,), dev)
+    st = lib.acx_mlp_scores(_ptr(x), _ptr(mlp.params_on(dev)), mlp.dims, mlp.n_layers, _ptr(out), M, _stream(dev))
+    _lib.check(st, "acx_mlp_scores")
+    return torch.expm1(out) if expm1 else out
+
+
 # ---------------------------------------------------------------------------------------------
 # exact word functions on arbitrary int32 letters (csrc/acx_words.hip)
 # ---------------------------------------------------------------------------------------------

@@ -2,16 +2,20 @@
 (csrc/acx_vgreedy.hip, C-ABI acx_vgreedy_* in include/acx.h): one wave owns one search -- node
 store, visited set, the heap of (score, path length, node index) -- and a step of all searches is
 two launches (pop, push) with the scorer between them, called once on every live search's candidates
-together.  Given equal scores, each result equals the reference's
+together -- or, with an acx.DeviceMLP as the scorer, launches of many pops each in which the device
+scores the candidates itself (acx_vgreedy_run_mlp).  Given equal scores, each result equals the reference's
 value_guided_greedy_search(p_i, ...) (value_search/value_guided_search.py:253-414, with
 solution_cache=None and time_limit=None), paths included: the pop order, the order-dependent dedup
 and the once-per-pop budget test are exact, and the only floats are the scorer's."""
 
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from .. import _lib
+from .._mlp import DeviceMLP
 from . import _batch_bfs, _cache, _scored
 
 _HANDLES = {}  # (device, L, cyclical) -> (handle, searches, max_nodes_each)
@@ -33,7 +37,7 @@ def release_workspaces() -> None:
 def value_guided_greedy_search_many(presentations, scorer, max_nodes_to_explore=10000,
                                     cyclically_reduce_after_moves=False, scorer_input="features", feat_mean=None,
                                     feat_std=None, device=None, on_error="raise", return_stats=False,
-                                    workspace_bytes=None, solution_cache=None):
+                                    workspace_bytes=None, solution_cache=None, fused=None, pops_per_launch=4096):
     """value_guided_greedy_search of every row of `presentations` ((N, 2L) array, tensor or list of
     equal-length rows), all searches stepping together: a list of (True, path) | (False, []), entry i
     equal to the reference's value_guided_greedy_search(presentations[i], ..., budget_i) wherever the
@@ -65,14 +69,26 @@ def value_guided_greedy_search_many(presentations, scorer, max_nodes_to_explore=
       ACX_BFS_CACHED, min_length 2 and nodes as for a found search (1 for a root hit).  Every
       search of the batch sees the cache as it was when the call began -- the reference's loop
       backfills between two searches; here the backfill follows the call (acx.SolutionCache).
-      With return_stats the dict gains cache_hit, an (N) bool array."""
+      With return_stats the dict gains cache_hit, an (N) bool array.
+    fused: with an acx.DeviceMLP as the scorer on scorer_input="features", the searches run on the
+      device alone: launches of up to pops_per_launch pops of every live search -- pop, features,
+      normalisation, the network (csrc/acx_mlp.h), push -- with one host read per launch instead of
+      one per pop, and the same results as the stepped loop with that scorer.  None (default): fused
+      exactly when it can be; False: the stepped loop; True with any other scorer or input:
+      ValueError.  The scores are the network's y, not expm1(y) (acx.DeviceMLP)."""
+    can_fuse = isinstance(scorer, DeviceMLP) and scorer_input == "features"
+    if fused and not can_fuse:
+        raise ValueError("fused=True needs an acx.DeviceMLP as the scorer and scorer_input='features'")
+    if int(pops_per_launch) < 1:
+        raise ValueError("pops_per_launch must be at least 1")
+    fused = (int(pops_per_launch),) if (can_fuse if fused is None else fused) else None
     states, budgets = _scored._validate_scorer(presentations, scorer, max_nodes_to_explore, scorer_input, on_error,
                                                _VGREEDY.name)
     _cache.check(solution_cache, states.shape[1] // 2)
     mean, std = _scored._validate_norm(scorer_input, feat_mean, feat_std)
     return _scored._run(_STEPS, states, budgets, (), (), scorer, scorer_input, mean, std,
                         cyclically_reduce_after_moves, device, workspace_bytes, on_error, return_stats,
-                        solution_cache=solution_cache)
+                        solution_cache=solution_cache, fused=fused)
 
 
 def _total_length(f):
@@ -82,7 +98,7 @@ def _total_length(f):
 def value_guided_greedy_search(presentation, model=None, architecture="mlp", feat_mean=None, feat_std=None,
                                max_nodes_to_explore=10000, device=None, use_length_priority=False,
                                cyclically_reduce_after_moves=False, verbose=False, solution_cache=None,
-                               time_limit=None):
+                               time_limit=None, fused=False):
     """The reference's value_guided_greedy_search (value_search/value_guided_search.py:253-414):
     (solved, path, stats) with stats = {'nodes_explored', 'min_length'}.  The candidates are scored
     as _score_states_mlp / _score_states_seq score them -- the model on the normalised features
@@ -95,12 +111,23 @@ def value_guided_greedy_search(presentation, model=None, architecture="mlp", fea
     solution_cache: an acx.SolutionCache (the reference's dict is refused with NotImplementedError:
     upload it once with acx.SolutionCache.from_dict, or hand it to the batch call, which uploads it
     for that call); on a hit the stats also hold 'cache_hit': True, as the reference's.  time_limit is accepted only as None; verbose prints
-    nothing."""
+    nothing.
+
+    fused=True: `model` (a FeatureMLP; architecture must be "mlp") becomes an acx.DeviceMLP and the search
+    runs on the device alone, ordered by the network's output y instead of expm1(y): the same
+    order as the exact scores', without float32 expm1's ties and overflow."""
+    many, scorer = value_guided_greedy_search_many, _total_length if use_length_priority else None
+    if fused:
+        if architecture != "mlp" or use_length_priority:
+            raise ValueError("fused=True needs architecture='mlp' and a model")
+        if model is None or feat_mean is None or feat_std is None:
+            raise ValueError("fused=True needs a model, feat_mean and feat_std")
+        scorer = DeviceMLP.from_module(model)
+        many = functools.partial(many, feat_mean=feat_mean, feat_std=feat_std, fused=True)
     solved, path, st = _scored._single(
-        "value_guided_greedy_search", value_guided_greedy_search_many, presentation, model, architecture, feat_mean,
+        "value_guided_greedy_search", many, presentation, model, architecture, feat_mean,
         feat_std, solution_cache, time_limit, dict(max_nodes_to_explore=max_nodes_to_explore),
-        no_model="a model is needed unless use_length_priority=True",
-        scorer=_total_length if use_length_priority else None,
+        no_model="a model is needed unless use_length_priority=True", scorer=scorer,
         cyclically_reduce_after_moves=cyclically_reduce_after_moves, device=device)
     stats = {"nodes_explored": st["nodes"], "min_length": st["min_length"]}
     if st.get("cache_hit"):

@@ -106,11 +106,13 @@ def _single(name, many, presentation, model, architecture, feat_mean, feat_std, 
 
 
 def _run(sc, states, budgets, own, extra, scorer, scorer_input, mean, std, cyclical, device, workspace_bytes, on_error,
-         return_stats, margs=None, solution_cache=None):
+         return_stats, margs=None, solution_cache=None, fused=None):
     """the validated searches, in groups that fit the workspace -> the call's return value.  `own`:
     the engine's per-search arrays for its begin call (beam: the widths), `extra`: its handle's
     shape arguments, `margs`: what its _Steps.make_args needs, `solution_cache`: what the caller
-    passed, already through _cache.check."""
+    passed, already through _cache.check.  `fused`: None, or (pops per launch,): `scorer` is an
+    acx.DeviceMLP and the engine's run_mlp call (vgreedy) steps the searches on the device, many
+    pops per launch, in place of the loop of steps."""
     eng = sc.eng
     N, L = states.shape[0], states.shape[1] // 2
     stats = {k: np.zeros(N, t) for k, t in (("status", np.int32), *sc.stats)}
@@ -126,7 +128,7 @@ def _run(sc, states, budgets, own, extra, scorer, scorer_input, mean, std, cycli
             for g0 in range(0, N, group):
                 g1 = min(N, g0 + group)
                 _run_group(sc, lib, dev, L, cyc, states[g0:g1], budgets[g0:g1], [x[g0:g1] for x in own], group, cap,
-                           extra, scorer, scorer_input, mean, std, g0, stats, results, margs, cache)
+                           extra, scorer, scorer_input, mean, std, g0, stats, results, margs, cache, fused)
         finally:
             if ours:
                 cache.close()
@@ -138,7 +140,7 @@ def _run(sc, states, budgets, own, extra, scorer, scorer_input, mean, std, cycli
 
 
 def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, scorer, scorer_input, mean, std, g0,
-               stats, results, margs=None, cache=None):
+               stats, results, margs=None, cache=None, fused=None):
     eng = sc.eng
     n, kw = len(states), _lib.key_words(L)
     h = _batch_bfs._handle(eng, lib, dev, L, cyc, n_cap, cap, extra)
@@ -156,28 +158,31 @@ def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, sc
             out = torch.zeros(2, dtype=torch.int64, device=dev)
             call("begin", st.data_ptr(), bd.data_ptr(), *(x.data_ptr() for x in own_d), n)
             mark = (lambda phase: None) if _TIMING is None else _TIMING.mark
-            for step in range(sc.bound(cap)):
-                mark("between")
-                call(sc.make, *(sc.make_args(dev, step, margs) if sc.make_args else ()), out.data_ptr())
-                mark(sc.make)
-                M, live = sc.report(*out.tolist())  # the step's one host synchronisation
-                if live == 0:
-                    break
-                if M == 0:  # nothing to score
-                    continue
-                keys = torch.empty((M, kw), dtype=torch.int64, device=dev)
-                call("gather", keys.data_ptr(), M)
-                if scorer_input == "features":
-                    x = ops.features(keys=keys, L=L, mean=mean_d, std=std_d)
-                else:
-                    x = ops.token_ids(keys=keys, L=L)
-                mark("gather_features")
-                y = _scores(scorer, x, M)
-                mark("scorer")
-                call(sc.take, y.data_ptr(), M)
-                mark(sc.take)
+            if fused is not None:
+                _fused_loop(sc, call, scorer, dev, mean_d, std_d, fused[0], cap, out, mark)
             else:
-                raise _lib.ACXError(f"{eng.prefix}: the searches did not end within their budgets")
+                for step in range(sc.bound(cap)):
+                    mark("between")
+                    call(sc.make, *(sc.make_args(dev, step, margs) if sc.make_args else ()), out.data_ptr())
+                    mark(sc.make)
+                    M, live = sc.report(*out.tolist())  # the step's one host synchronisation
+                    if live == 0:
+                        break
+                    if M == 0:  # nothing to score
+                        continue
+                    keys = torch.empty((M, kw), dtype=torch.int64, device=dev)
+                    call("gather", keys.data_ptr(), M)
+                    if scorer_input == "features":
+                        x = ops.features(keys=keys, L=L, mean=mean_d, std=std_d)
+                    else:
+                        x = ops.token_ids(keys=keys, L=L)
+                    mark("gather_features")
+                    y = _scores(scorer, x, M)
+                    mark("scorer")
+                    call(sc.take, y.data_ptr(), M)
+                    mark(sc.take)
+                else:
+                    raise _lib.ACXError(f"{eng.prefix}: the searches did not end within their budgets")
             status = torch.empty(n, dtype=torch.int32, device=dev)
             min_len = torch.empty(n, dtype=torch.int32, device=dev)
             nodes, steps, plen = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
@@ -191,6 +196,20 @@ def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, sc
     finally:  # the handle outlives the call and the cache may not: it never keeps a pointer to it
         if sc.cache and cache is not None:
             eng.fn(lib, "set_cache")(h, None)
+
+
+def _fused_loop(sc, call, mlp, dev, mean_d, std_d, pops_per_launch, cap, out, mark):
+    """launches of up to pops_per_launch pops of every live search until none is live: one host read
+    per launch.  The engine's step bound, in pops, bounds the launches."""
+    params = mlp.params_on(dev)
+    for _ in range(-(-sc.bound(cap) // pops_per_launch)):
+        call("run_mlp", params.data_ptr(), mlp.dims, mlp.n_layers, ops._ptr(mean_d), ops._ptr(std_d),
+             pops_per_launch, out.data_ptr())
+        _, live = out.tolist()  # (pops of this launch, live searches): the launch's host synchronisation
+        mark("run_mlp")
+        if live == 0:
+            return
+    raise _lib.ACXError(f"{sc.eng.prefix}: the searches did not end within their budgets")
 
 
 def _cache_hits(eng, lib, h, dev, stream, cache, g0, n, stats, results):

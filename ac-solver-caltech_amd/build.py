@@ -20,7 +20,8 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "acx", "libacx.so")
 INCLUDE = os.path.join(REPO, "include")
 SOURCES = ["acx_kernels.hip", "acx_bfs.hip", "acx_mbfs.hip", "acx_mgreedy.hip", "acx_beam.hip", "acx_vgreedy.hip",
-           "acx_mcts.hip", "acx_cache.hip", "acx_sbfs.hip", "acx_features.hip", "acx_curriculum.hip", "acx_words.hip", "acx_greedy.hip", "acx_search.cpp"]
+           "acx_mcts.hip", "acx_cache.hip", "acx_sbfs.hip", "acx_features.hip", "acx_mlp.hip", "acx_curriculum.hip",
+           "acx_words.hip", "acx_greedy.hip", "acx_search.cpp", "acx_mlp_host.cpp"]
 # acx_kernels.hip is also compiled once per instantiation part (-DACX_PART=n, see the part table
 # and its "extern template" block in acx_launch.h), in parallel: the runtime-L generic sets took
 # ~7 minutes in one object

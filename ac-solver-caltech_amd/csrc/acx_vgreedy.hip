@@ -77,6 +77,20 @@
 // the popped node plus the child's (action, total), and the hit record (entry, rel, k) goes to the
 // attachment's array, not to the search's slice.  vgreedy_pop_cached_kernel<1 / 2 / 3 / 4 / 8>:
 // 53 / 55 / 57 / 59 / 68 VGPRs, the same LDS (profiles/cache/kernel_resources.md).
+//
+// Fused with the FeatureMLP scorer (acx_vgreedy_run_mlp; acx_mlp.h, acx_feat.h): the pop and push
+// kernels' bodies are device functions, and vgreedy_fused_kernel<NW> / vgreedy_fused_cached_kernel<NW>
+// loop them in one launch, up to max_pops times per search, with the scorer between them on the
+// device: 4 candidates at a time, lane c computes candidate c's 14 features from its store row
+// (acx_features' arithmetic, normalisation included) into LDS, the wave runs the layers, and lane c
+// keeps y; the push reads the pop's scores from LDS.  Nothing returns to the host between pops; lane 0
+// adds the search's pops and whether it is still live to the call's pair.  A launch is bounded by
+// max_pops, never by a budget, and the state a launch leaves is the state a push leaves: stepped and
+// fused calls may alternate on a handle.
+// vgreedy_fused_kernel<1 / 2 / 3 / 4 / 8>   126 / 128 / 130 / 132 / 169 VGPRs, 4,432 / 4,528 / 4,624 /
+//       4,720 / 5,104 B of LDS (the pop's + 4,096 B of activations + 48 B of scores), no scratch but
+//       <2>'s 24 B, which are pop_body<2>'s; vgreedy_fused_cached_kernel 128 / 133 / 166 / 167 / 171
+//       VGPRs, the same LDS (profiles/fused_mlp/kernel_resources.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -87,7 +101,9 @@
 #include "acx_beam_key.h"
 #include "acx_bfs_common.h"
 #include "acx_cache.h"
+#include "acx_feat.h"
 #include "acx_heap.h"
+#include "acx_mlp.h"
 #include "acx_pop.h"
 #include "acx_scored.h"
 #include "acx_visited.h"
@@ -281,13 +297,16 @@ __global__ __launch_bounds__(GT) void vgreedy_pop_cached_kernel(Args a, cache::A
     pop_body<NW, true>(a, at);
 }
 
-__global__ __launch_bounds__(GT) void vgreedy_push_kernel(Args a, const float* scores, int64_t M) {
+// The push kernel's body: the scores of search q's candidates are scores[off ..], off the search's
+// offset (acx_scored.h) or, FUSED, 0: the fused kernel's scores are the search's own M = 12 slots.
+template <bool FUSED>
+__device__ __forceinline__ void push_body(const Args& a, const float* scores, int64_t M) {
     const int lane = threadIdx.x;
     const int64_t q = blockIdx.x;
     State* S = a.state + q;
     if (S->done) return;
     const int n = a.counts[q];  // 0 for a pop without a candidate
-    const int64_t off = a.offsets[q];
+    const int64_t off = FUSED ? 0 : a.offsets[q];
     const int64_t hn = S->hn, base = S->cand_base, n_nodes = S->n_nodes, max_nodes = S->max_nodes;
     if (n == 0) return;
     const int64_t steps = S->steps;
@@ -325,6 +344,82 @@ __global__ __launch_bounds__(GT) void vgreedy_push_kernel(Args a, const float* s
         S->hn = hn + n;
         S->cand_n = 0;
     }
+}
+
+__global__ __launch_bounds__(GT) void vgreedy_push_kernel(Args a, const float* scores, int64_t M) {
+    push_body<false>(a, scores, M);
+}
+
+// Up to max_pops pops of search q in one launch, scored by the network (acx_mlp.h): per pop the pop
+// kernel's body, then, 4 candidates at a time, lane c's candidate's features from its store row
+// (acx_feat.h: acx_features' arithmetic, normalisation included) into LDS and the layers, lane c
+// keeping y; then the push kernel's body over the pop's scores.  Lane 0 adds the pops done and
+// whether the search is still live to pair.
+template <int NW, bool CACHE>
+__device__ __forceinline__ void fused_body(const Args& a, const cache::Attach& at, const mlp::Net& net,
+                                           const float* mean, const float* stdv, int64_t max_pops,
+                                           unsigned long long* pair) {
+    __shared__ __attribute__((aligned(16))) float act[mlp::MAX_W][mlp::G];
+    __shared__ float sc[12];
+    const int lane = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    const State* S = a.state + q;
+    const uint64_t* store = a.store + q * a.rows * a.kw;
+    int64_t pops = 0;
+    bool done = S->done != 0;
+    __syncthreads();  // the state is read before lane 0 rewrites it
+    while (!done && pops < max_pops) {
+        pop_body<NW, CACHE>(a, at);
+        ++pops;
+        __syncthreads();
+        done = S->done != 0;
+        const int n = done ? 0 : min(a.counts[q], 12);
+        const int64_t base = S->cand_base;
+        for (int c0 = 0; c0 < n; c0 += mlp::G) {  // (uniform)
+            __syncthreads();  // the last candidates' chains have read act
+            if (lane < mlp::G) {
+                float f[feat::NF] = {};
+                if (c0 + lane < n && base + c0 + lane < a.rows) {  // (the second: always)
+                    PresRegs<NW> p;
+                    load_key<NW>(store + (base + c0 + lane) * a.kw, a.kw, a.L, p);
+                    feat::Counts k;
+                    k.n[0] = p.n0;
+                    k.n[1] = p.n1;
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; ++c) {
+                        k.c[0][c] = feat::count_code<NW>(p.w0, p.n0, c);
+                        k.c[1][c] = feat::count_code<NW>(p.w1, p.n1, c);
+                    }
+                    feat::write_features(k, f, mean, stdv);
+                }
+#pragma unroll
+                for (int i = 0; i < feat::NF; ++i) act[i][lane] = f[i];
+            }
+            __syncthreads();
+            const float y = mlp::forward(net, act, lane);
+            if (lane < mlp::G && c0 + lane < n) sc[c0 + lane] = y;
+        }
+        __syncthreads();
+        if (n > 0) push_body<true>(a, sc, 12);
+        __syncthreads();
+        done = S->done != 0;
+    }
+    if (lane == 0) {
+        atomicAdd(pair, (unsigned long long)pops);
+        if (!done) atomicAdd(pair + 1, 1ull);
+    }
+}
+
+template <int NW>
+__global__ __launch_bounds__(GT) void vgreedy_fused_kernel(Args a, mlp::Net net, const float* mean, const float* stdv,
+                                                           int64_t max_pops, unsigned long long* pair) {
+    fused_body<NW, false>(a, cache::Attach{}, net, mean, stdv, max_pops, pair);
+}
+template <int NW>
+__global__ __launch_bounds__(GT) void vgreedy_fused_cached_kernel(Args a, cache::Attach at, mlp::Net net,
+                                                                  const float* mean, const float* stdv,
+                                                                  int64_t max_pops, unsigned long long* pair) {
+    fused_body<NW, true>(a, at, net, mean, stdv, max_pops, pair);
 }
 
 // what the handle (acx_batch.h) and the step frame (acx_scored.h) need of this engine
@@ -373,6 +468,32 @@ struct PopCached {
     void go() { vgreedy_pop_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at); }
 };
 
+struct Fused {
+    const Args& a;
+    hipStream_t st;
+    mlp::Net net;
+    const float *mean, *stdv;
+    int64_t max_pops;
+    unsigned long long* pair;
+    template <int NW>
+    void go() {
+        vgreedy_fused_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, net, mean, stdv, max_pops, pair);
+    }
+};
+struct FusedCached {
+    const Args& a;
+    hipStream_t st;
+    cache::Attach at;
+    mlp::Net net;
+    const float *mean, *stdv;
+    int64_t max_pops;
+    unsigned long long* pair;
+    template <int NW>
+    void go() {
+        vgreedy_fused_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at, net, mean, stdv, max_pops, pair);
+    }
+};
+
 }  // namespace vgreedy
 }  // namespace acx
 
@@ -419,6 +540,25 @@ int acx_vgreedy_push(void* h, const float* scores, int64_t M, void* stream) {
     return scored::take<Engine>(h, scores, M, stream, [=](const vgreedy::Args& a, hipStream_t st) {
         vgreedy::vgreedy_push_kernel<<<dim3((unsigned)a.n), dim3(vgreedy::GT), 0, st>>>(a, scores, M);
     });
+}
+
+int acx_vgreedy_run_mlp(void* h, const float* params, const int32_t* dims, int32_t n_layers, const float* mean,
+                        const float* stdv, int64_t max_pops, int64_t* pair, void* stream) {
+    batch::Handle<Engine>* S = static_cast<batch::Handle<Engine>*>(h);
+    if (!S || !acx::mlp::aligned(params) || !acx::mlp::valid(dims, n_layers) || (!mean != !stdv) || max_pops < 1 || !pair)
+        return ACX_E_ARG;
+    const vgreedy::Args& a = S->a;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(pair);
+    if (hipMemsetAsync(out, 0, 16, st) != hipSuccess) return ACX_E_LAUNCH;
+    if (a.n == 0) return ACX_OK;
+    const acx::mlp::Net net = acx::mlp::net_of(params, dims, n_layers);
+    acx::cache::Attach at;
+    if (acx::cache::attached(S, at))
+        acx::bfs::by_nw(a.L, vgreedy::FusedCached{a, st, at, net, mean, stdv, max_pops, out});
+    else
+        acx::bfs::by_nw(a.L, vgreedy::Fused{a, st, net, mean, stdv, max_pops, out});
+    return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 
 int acx_vgreedy_finish(void* h, int32_t* status, int64_t* nodes, int64_t* steps, int32_t* min_length,

@@ -635,6 +635,38 @@ int acx_vgreedy_paths(void* h, int64_t n, const int64_t* offsets, int32_t* actio
 void acx_vgreedy_destroy(void* h);
 
 /*
+ * The FeatureMLP scorer (value_search/value_network.py, FeatureMLP) in one exact float32
+ * arithmetic, on the device and on the host (csrc/acx_mlp.h, acx_mlp.hip, acx_mlp_host.cpp).  A
+ * network is n_layers layers, 2 <= n_layers <= 5; `dims` HOST (n_layers + 1) int32 holds the widths:
+ * dims[0] = 14, every hidden width a multiple of 64 up to 256, dims[n_layers] = 1.  `params` is one
+ * float32 buffer: per layer W transposed (k-major, K x H), then the bias (H).  Every output j of
+ * every layer is acc = bias[j], then acc = fmaf(W[k][j], x[k], acc) for k = 0 .. K-1 in ascending
+ * order, and v < 0 ? 0 : v after a hidden layer (a NaN and -0.0 pass); the result is the last
+ * layer's output y.  The reference scores with expm1(y): y orders as its exact scores do, without
+ * float32 expm1's ties between neighbours and its +inf above about 88.7.
+ *   acx_mlp_scores       `x` DEVICE (M, 14) float32, the features as the network takes them
+ *                        (already normalised), `params` DEVICE, `out` DEVICE (M) float32.
+ *   acx_mlp_scores_host  the same on host memory, bit for bit; needs no GPU.
+ *   acx_vgreedy_run_mlp  (value_guided_search.py:339-411) on a handle acx_vgreedy_begin has set up:
+ *                        up to max_pops >= 1 pops of every search that has not ended, in one launch
+ *                        and with no scorer call: per pop what acx_vgreedy_pop does, the features of
+ *                        the pop's candidates as acx_features computes them from their keys
+ *                        ((f - mean) / std with `mean`, `stdv` DEVICE (14) float32; both or neither),
+ *                        the network, and what acx_vgreedy_push does with its y as the scores.
+ *                        `pair` DEVICE (2) int64 receives the pops of this launch, summed over the
+ *                        searches, and the number of searches that have not ended.  The handle's state
+ *                        persists between launches; finish, paths, set_cache and cache_hits are the
+ *                        calls above.
+ * ACX_E_ARG for dims or n_layers outside the limits, a NULL params, M < 0, or max_pops < 1.
+ */
+int acx_mlp_scores(const float* x, const float* params, const int32_t* dims, int32_t n_layers, float* out, int64_t M,
+                   void* stream);
+int acx_mlp_scores_host(const float* x, const float* params, const int32_t* dims, int32_t n_layers, float* out,
+                        int64_t M);
+int acx_vgreedy_run_mlp(void* h, const float* params, const int32_t* dims, int32_t n_layers, const float* mean,
+                        const float* stdv, int64_t max_pops, int64_t* pair, void* stream);
+
+/*
  * MCTS over a batch of presentations, scored by the caller (csrc/acx_mcts.hip): one wave owns one
  * search -- node store, visited set and the tree's records (value sum, visit count, prior, the
  * children's rows) -- on a private slice of the handle's workspace, and a step of all searches is
