@@ -30,7 +30,7 @@ _BEAM = _batch_bfs._Engine("beam_search_many", "acx_beam", _HANDLES, (_lib.BFS_F
 # expand writes the candidates' number M, and the searches are over when there are none; a step
 # without a verdict adds a node to a search, and a search ends at its budget: budget + 2 steps
 _STEPS = _scored._Steps(_BEAM, "expand", "select", lambda M, _: (M, M), 2,
-                        (("nodes", np.int64), ("steps", np.int64)), cache=True)
+                        (("nodes", np.int64), ("steps", np.int64)))
 
 
 def release_workspaces() -> None:

@@ -48,7 +48,7 @@ def _select_args(dev, step, c_explore):
 # select writes (M, live); M == 0 with live searches: launches of dead ends.  A launch gives a search
 # at least one new node, its ending, or MCTS_SPIN of its at most 50 * budget iterations
 _STEPS = _scored._Steps(_MCTS, "select", "backup", lambda M, live: (M, live), lambda cap: cap + 50 * cap // 64 + 3,
-                        (("nodes", np.int64), ("iterations", np.int64)), make_args=_select_args, cache=True)
+                        (("nodes", np.int64), ("iterations", np.int64)), make_args=_select_args)
 
 
 def release_workspaces() -> None:

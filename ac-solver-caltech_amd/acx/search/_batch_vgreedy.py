@@ -26,7 +26,7 @@ _VGREEDY = _batch_bfs._Engine("value_guided_greedy_search_many", "acx_vgreedy", 
 # pop writes (M, live); M == 0 with live searches: pops whose children were all known.  A pop takes
 # one of a search's at most budget + 11 nodes off its heap: budget + 13 steps
 _STEPS = _scored._Steps(_VGREEDY, "pop", "push", lambda M, live: (M, live), 13,
-                        (("nodes", np.int64), ("steps", np.int64), ("min_length", np.int32)), cache=True)
+                        (("nodes", np.int64), ("steps", np.int64), ("min_length", np.int32)))
 
 
 def release_workspaces() -> None:

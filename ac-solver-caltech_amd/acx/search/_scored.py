@@ -22,12 +22,11 @@ class _Steps:
     largest budget, or a function of the largest budget -- with its reason, and the stats it
     returns besides status.  `make_args(dev, step, margs)`: the engine's own arguments of its make
     call at step `step`, before the output pair (mcts: the log table and the constant), from what
-    its entry passed to _run as `margs`.  `cache`: the engine has acx_*_set_cache / _cache_hits
+    its entry passed to _run as `margs`.  Every engine has acx_*_set_cache / _cache_hits
     (csrc/acx_cache.h) and its searches take a solution cache."""
 
-    def __init__(self, eng, make, take, report, bound, stats, make_args=None, cache=False):
+    def __init__(self, eng, make, take, report, bound, stats, make_args=None):
         self.eng, self.make, self.take, self.report, self.stats = eng, make, take, report, stats
-        self.cache = cache
         self.bound = bound if callable(bound) else (lambda cap: cap + bound)
         self.make_args = make_args
 
@@ -144,9 +143,9 @@ def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, sc
     eng = sc.eng
     n, kw = len(states), _lib.key_words(L)
     h = _batch_bfs._handle(eng, lib, dev, L, cyc, n_cap, cap, extra)
-    if sc.cache:  # a reused handle keeps its attachment: set it, or clear it, for this run
-        _lib.check(eng.fn(lib, "set_cache")(h, cache.attach_to(dev) if cache is not None else None),
-                   f"{eng.prefix}_set_cache")
+    # a reused handle keeps its attachment: set it, or clear it, for this run
+    _lib.check(eng.fn(lib, "set_cache")(h, cache.attach_to(dev) if cache is not None else None),
+               f"{eng.prefix}_set_cache")
     try:
         stream = torch.cuda.current_stream(dev).cuda_stream
         call = lambda what, *args: _lib.check(eng.fn(lib, what)(h, *args, stream), f"{eng.prefix}_{what}")  # noqa: E731
@@ -194,7 +193,7 @@ def _run_group(sc, lib, dev, L, cyc, states, budgets, own, n_cap, cap, extra, sc
             if cache is not None:
                 _cache_hits(eng, lib, h, dev, stream, cache, g0, n, stats, results)
     finally:  # the handle outlives the call and the cache may not: it never keeps a pointer to it
-        if sc.cache and cache is not None:
+        if cache is not None:
             eng.fn(lib, "set_cache")(h, None)
 
 

@@ -306,15 +306,6 @@ static bool new_epoch(Handle<E>* S, hipStream_t st) {
 }
 
 template <class E>
-struct RunLaunch {
-    const typename E::Args& a;
-    int64_t n;
-    hipStream_t st;
-    template <int NW>
-    void go() { E::template launch<NW>(a, n, st); }
-};
-
-template <class E>
 static int run(void* h, const int32_t* states, const int64_t* budgets, int64_t n, int32_t* status, int64_t* nodes,
                int64_t* parents, int32_t* min_length, int64_t* path_len, void* stream) {
     Handle<E>* S = static_cast<Handle<E>*>(h);
@@ -331,7 +322,7 @@ static int run(void* h, const int32_t* states, const int64_t* budgets, int64_t n
     a.parents = parents;
     a.min_length = min_length;
     a.path_len = path_len;
-    by_nw(a.L, RunLaunch<E>{a, n, st});
+    by_nw(a.L, [&](auto nw) { E::template launch<decltype(nw)::value>(a, n, st); });
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 

@@ -4,10 +4,10 @@
 //
 // Reference: value_search/value_guided_search.py:417-561 (beam_search) with time_limit=None; the
 // solution cache is the second instantiation of the begin and expand kernels (begin_body /
-// expand_body below; beam_expand_cached_kernel<1 / 2 / 3 / 4 / 8>: 84 / 90 / 92 / 94 / 136 VGPRs,
-// profiles/cache/kernel_resources.md).  The root is node 0 and total_nodes starts at 1; while total_nodes <
-// max_nodes a step makes the beam's children in sequential order s = 12 * (rank in the beam) +
-// action, and for each in that order: a raising move ends the search (ACX_BFS_MOVE_ERROR); a child
+// expand_body below; beam_expand_kernel<1 / 2 / 3 / 4 / 8, cache::Attach>: 84 / 90 / 92 / 94 / 136
+// VGPRs, profiles/cache/kernel_resources.md, where its name has _cached before _kernel).  The root
+// is node 0 and total_nodes starts at 1; while total_nodes < max_nodes a step makes the beam's
+// children in sequential order s = 12 * (rank in the beam) + action, and for each in that order: a raising move ends the search (ACX_BFS_MOVE_ERROR); a child
 // of total length 2 ends it, found, before the visited test; a child not yet visited becomes the
 // next node and the step's next candidate; if that makes total_nodes >= max_nodes the expansion
 // stops at that child (bfs tests after each parent: acx_bfs_verdict.h is not what happens here).
@@ -116,13 +116,9 @@ __device__ __forceinline__ void begin_body(const Args& a, const int32_t* widths,
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* widths) {
-    begin_body<NW, false>(a, widths, cache::Attach{});
-}
-template <int NW>
-__global__ __launch_bounds__(TPB) void beam_begin_cached_kernel(Args a, const int32_t* widths, cache::Attach at) {
-    begin_body<NW, true>(a, widths, at);
+template <int NW, class... At>
+__global__ __launch_bounds__(TPB) void beam_begin_kernel(Args a, const int32_t* widths, At... at) {
+    begin_body<NW, sizeof...(At) != 0>(a, widths, cache::attach_of(at...));
 }
 
 template <int NW, bool CACHE>
@@ -295,13 +291,9 @@ __device__ __forceinline__ void expand_body(const Args& a, const cache::Attach& 
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a) {
-    expand_body<NW, false>(a, cache::Attach{});
-}
-template <int NW>
-__global__ __launch_bounds__(TPB) void beam_expand_cached_kernel(Args a, cache::Attach at) {
-    expand_body<NW, true>(a, at);
+template <int NW, class... At>
+__global__ __launch_bounds__(TPB) void beam_expand_kernel(Args a, At... at) {
+    expand_body<NW, sizeof...(At) != 0>(a, cache::attach_of(at...));
 }
 
 template <int CAP, int THREADS>
@@ -379,35 +371,6 @@ static bool shape(Args& a, int32_t L, int64_t B, int32_t W, int32_t cyclical) {
     return batch::shape<Engine>(a, L, B, cyclical);
 }
 
-struct Begin {
-    const Args& a;
-    hipStream_t st;
-    const int32_t* widths;
-    template <int NW>
-    void go() { beam_begin_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a, widths); }
-};
-struct Expand {
-    const Args& a;
-    hipStream_t st;
-    template <int NW>
-    void go() { beam_expand_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a); }
-};
-struct BeginCached {
-    const Args& a;
-    hipStream_t st;
-    const int32_t* widths;
-    cache::Attach at;
-    template <int NW>
-    void go() { beam_begin_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a, widths, at); }
-};
-struct ExpandCached {
-    const Args& a;
-    hipStream_t st;
-    cache::Attach at;
-    template <int NW>
-    void go() { beam_expand_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(TPB), 0, st>>>(a, at); }
-};
-
 }  // namespace beam
 }  // namespace acx
 
@@ -432,10 +395,11 @@ void acx_beam_destroy(void* h) { batch::destroy<beam::Engine>(h); }
 
 int acx_beam_begin(void* h, const int32_t* states, const int64_t* budgets, const int32_t* widths, int64_t n,
                    void* stream) {
-    acx::cache::Attach at;
-    if (h && acx::cache::attached(static_cast<batch::Handle<beam::Engine>*>(h), at))
-        return scored::begin<beam::Engine, beam::BeginCached>(h, states, budgets, widths != nullptr, n, stream, widths, at);
-    return scored::begin<beam::Engine, beam::Begin>(h, states, budgets, widths != nullptr, n, stream, widths);
+    return scored::begin<beam::Engine>(h, states, budgets, widths != nullptr, n, stream,
+                                       [=](auto nw, const beam::Args& a, auto... at) {
+        beam::beam_begin_kernel<decltype(nw)::value>
+            <<<dim3((unsigned)a.n), dim3(acx::bfs::TPB), 0, (hipStream_t)stream>>>(a, widths, at...);
+    });
 }
 
 int acx_beam_set_cache(void* h, void* cache) { return acx::cache::set_cache<batch::Handle<beam::Engine>>(h, cache); }
@@ -445,10 +409,10 @@ int acx_beam_cache_hits(void* h, int64_t n, int64_t* entry, int32_t* rel, int32_
 }
 
 int acx_beam_expand(void* h, int64_t* total, void* stream) {
-    acx::cache::Attach at;
-    if (h && acx::cache::attached(static_cast<batch::Handle<beam::Engine>*>(h), at))
-        return scored::make<beam::Engine, beam::ExpandCached>(h, total, stream, at);
-    return scored::make<beam::Engine, beam::Expand>(h, total, stream);
+    return scored::make<beam::Engine>(h, total, stream, [=](auto nw, const beam::Args& a, auto... at) {
+        beam::beam_expand_kernel<decltype(nw)::value>
+            <<<dim3((unsigned)a.n), dim3(acx::bfs::TPB), 0, (hipStream_t)stream>>>(a, at...);
+    });
 }
 
 int acx_beam_gather(void* h, uint64_t* keys, int64_t M, void* stream) {

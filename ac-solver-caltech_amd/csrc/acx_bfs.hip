@@ -587,38 +587,18 @@ static bool dalloc(T*& p, size_t n) {
 
 // launches of one chunk (number k), templated on the key-word bound; the grids cover `ntiles`
 // tiles, an upper bound on the chunk's real tile count (the kernels read the real one, Live)
-struct ChunkLaunch {
-    Search* S;
-    hipStream_t st;
-    int64_t k;
-    int ntiles;
-    template <int NW>
-    void go() {
-        Args& a = S->a;
-        const unsigned wb = (unsigned)((ntiles + TPB / WAVE - 1) / (TPB / WAVE));
-        const int64_t nc = (int64_t)ntiles * TILE_CH;
-        bfs_expand_kernel<NW><<<dim3((unsigned)ntiles), dim3(TPB), 0, st>>>(a);
-        bfs_insert_kernel<NW + 1><<<dim3((unsigned)((nc + TPB - 1) / TPB)), dim3(TPB), 0, st>>>(a);
-        bfs_count_kernel<<<dim3(wb), dim3(TPB), 0, st>>>(a);
-        bfs_scan_kernel<<<dim3(1), dim3(1024), 0, st>>>(a);
-        bfs_commit_kernel<<<dim3(wb), dim3(TPB), 0, st>>>(a);
-        bfs_close_kernel<NW><<<dim3(1), dim3(256), 0, st>>>(a, k, S->mirror, S->trace_host);
-    }
-};
-struct RootLaunch {
-    Search* S;
-    hipStream_t st;
-    RootKey rk;
-    template <int NW>
-    void go() { bfs_root_kernel<NW + 1><<<dim3(1), dim3(64), 0, st>>>(S->a, rk); }
-};
-struct PathLaunch {
-    Search* S;
-    hipStream_t st;
-    int64_t node;
-    template <int NW>
-    void go() { bfs_path_kernel<NW><<<dim3(1), dim3(64), 0, st>>>(S->a, node, S->path_dev, PATH_CAP, S->path_n_dev); }
-};
+template <int NW>
+static void chunk_launch(Search* S, hipStream_t st, int64_t k, int ntiles) {
+    Args& a = S->a;
+    const unsigned wb = (unsigned)((ntiles + TPB / WAVE - 1) / (TPB / WAVE));
+    const int64_t nc = (int64_t)ntiles * TILE_CH;
+    bfs_expand_kernel<NW><<<dim3((unsigned)ntiles), dim3(TPB), 0, st>>>(a);
+    bfs_insert_kernel<NW + 1><<<dim3((unsigned)((nc + TPB - 1) / TPB)), dim3(TPB), 0, st>>>(a);
+    bfs_count_kernel<<<dim3(wb), dim3(TPB), 0, st>>>(a);
+    bfs_scan_kernel<<<dim3(1), dim3(1024), 0, st>>>(a);
+    bfs_commit_kernel<<<dim3(wb), dim3(TPB), 0, st>>>(a);
+    bfs_close_kernel<NW><<<dim3(1), dim3(256), 0, st>>>(a, k, S->mirror, S->trace_host);
+}
 }  // namespace bfs
 }  // namespace acx
 
@@ -685,8 +665,8 @@ int acx_bfs_run(void* h, const int32_t* presentation, int64_t max_nodes, int32_t
     hipStream_t st = (hipStream_t)stream;
     Args& a = S->a;
     const int L = S->L, kw = S->kw;
-    RootLaunch rl{S, st, {}};
-    acx::pack_key(presentation, L, kw, rl.rk.w);
+    RootKey rk{};
+    acx::pack_key(presentation, L, kw, rk.w);
     int total0 = 0;
     for (int i = 0; i < 2 * L; ++i) total0 += presentation[i] != 0;
 
@@ -696,7 +676,7 @@ int acx_bfs_run(void* h, const int32_t* presentation, int64_t max_nodes, int32_t
         S->fin_pending = false;
     }
     if (!acx::visited::next_epoch(S->epoch, a.table, S->tsize * 8, st, a.ep)) return ACX_E_LAUNCH;
-    by_nw(L, rl);
+    by_nw(L, [&](auto nw) { bfs_root_kernel<decltype(nw)::value + 1><<<dim3(1), dim3(64), 0, st>>>(a, rk); });
     bfs_init_kernel<<<dim3(1), dim3(64), 0, st>>>(a, max_nodes, S->pmax, (uint32_t)total0);
 
     // Chunks are enqueued one ahead of the one the host waits for: chunk k + 1 is in the stream
@@ -709,8 +689,7 @@ int acx_bfs_run(void* h, const int32_t* presentation, int64_t max_nodes, int32_t
     int64_t enqueued = 0;  // chunk numbers this search has used
     auto enqueue = [&](int64_t k, int64_t avail_ub) -> int {
         const int64_t pub = avail_ub < S->pmax ? avail_ub : S->pmax;
-        ChunkLaunch cl{S, st, S->kbase + k, (int)((pub - 1) / TILE + 2)};
-        by_nw(L, cl);
+        by_nw(L, [&](auto nw) { chunk_launch<decltype(nw)::value>(S, st, S->kbase + k, (int)((pub - 1) / TILE + 2)); });
         enqueued = k + 1;
         return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
     };
@@ -778,8 +757,10 @@ int acx_bfs_run(void* h, const int32_t* presentation, int64_t max_nodes, int32_t
     const uint32_t nt = lv.ntrace < (uint32_t)TRACE_CAP ? lv.ntrace : TRACE_CAP;
     for (uint32_t i = 0; i < nt; ++i) S->trace.push_back(S->trace_host[i]);
     if (status == ACX_BFS_FOUND) {
-        PathLaunch pl{S, st, succ_node};
-        by_nw(L, pl);
+        by_nw(L, [&](auto nw) {
+            bfs_path_kernel<decltype(nw)::value><<<dim3(1), dim3(64), 0, st>>>(a, succ_node, S->path_dev, PATH_CAP,
+                                                                                S->path_n_dev);
+        });
         if (hipGetLastError() != hipSuccess) return finish(ACX_E_LAUNCH);
     }
     const int fin_rc = finish(ACX_OK);  // the stream is idle from here on

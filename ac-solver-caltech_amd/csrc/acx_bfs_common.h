@@ -9,6 +9,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "acx.h"
 #include "acx_key.h"
 #include "acx_moves.h"
@@ -207,14 +209,16 @@ __device__ __forceinline__ uint32_t block_min(uint32_t v, uint32_t* sh) {
 
 static inline int nw_for(int L) { return L <= 16 ? 1 : L <= 32 ? 2 : L <= 48 ? 3 : L <= 64 ? 4 : 8; }
 
+// f(std::integral_constant<int, NW>{}) for the key-word count of L: a call site is a generic lambda
+// that launches its kernel's instantiation, [&](auto nw) { k<decltype(nw)::value><<<..>>>(..); }
 template <class F>
 static void by_nw(int L, F&& f) {
     switch (nw_for(L)) {
-        case 1: f.template go<1>(); break;
-        case 2: f.template go<2>(); break;
-        case 3: f.template go<3>(); break;
-        case 4: f.template go<4>(); break;
-        default: f.template go<8>(); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
     }
 }
 

@@ -175,9 +175,9 @@ __device__ __forceinline__ Hit probe(const View& c, const uint64_t* key, int kw,
 
 // ---------------------------------------------------------------------------------------------
 // A cache attached to a handle of a scored engine (acx_{vgreedy,beam,mcts}_set_cache).  The
-// engine's kernels have a second instantiation that takes an Attach after their Args and probes
-// where the reference looks (the engine's file says where); the instantiation without a cache is
-// the device code it was.  The probe is called from the kernels and not folded into pop::expand:
+// engine's begin and make kernels, and the fused one, have a second instantiation that takes an
+// Attach (last; the fused kernel: second) and probes where the reference looks (the engine's file says where); the instantiation
+// without a cache is the device code it was.  The probe is called from the kernels and not folded into pop::expand:
 // acx_pop.h records what a shared routine between expand and append cost these kernels.
 // The hit records belong to the attachment, one per search of the handle, not to the engines'
 // slices: the engines' bytes formulas do not change.
@@ -186,6 +186,12 @@ struct Attach {
     View view;
     Hit* hit;  // (n_cap)
 };
+
+// what a kernel template with the parameters `At... at` -- nothing, or an Attach -- hands its
+// body: body<NW, sizeof...(At) != 0>(.., attach_of(at...)).  The instantiation without a cache takes
+// no such argument.
+__device__ __forceinline__ Attach attach_of() { return Attach{}; }
+__device__ __forceinline__ const Attach& attach_of(const Attach& at) { return at; }
 
 // search q ends on a cache hit (one thread): the path reader returns the path to `node` plus
 // (act, tot), the state that hit; a root hit (plen == 0) returns no path at all -- the record
@@ -252,7 +258,7 @@ static int set_cache(void* h, void* cache) {
 }
 
 // the attachment of a handle as its kernels take it (read when a call begins: the cache may have
-// grown since it was attached); false: none
+// grown since it was attached); false: none.  scored::launch_by_cache (acx_scored.h) is its reader.
 template <class H>
 static bool attached(const H* S, Attach& out) {
     if (!S->cache) return false;

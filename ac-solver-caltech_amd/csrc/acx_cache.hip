@@ -260,52 +260,13 @@ static __global__ __launch_bounds__(TPB) void cache_entries_kernel(const uint64_
     if ((int64_t)pos < cap) out[pos] = (int64_t)visited::entry_code(v);
 }
 
-struct Replay {
-    const FillArgs& a;
-    bool emit;
-    hipStream_t st;
-    template <int NW>
-    void go() {
-        if (emit) cache_replay_kernel<NW, true><<<dim3((unsigned)a.P), dim3(GT), 0, st>>>(a);
-        else cache_replay_kernel<NW, false><<<dim3((unsigned)a.P), dim3(GT), 0, st>>>(a);
-    }
-};
-struct Insert {
-    Handle* S;
-    int64_t row0, n;
-    hipStream_t st;
-    template <int NW>
-    void go() {
-        cache_insert_kernel<NW + 1><<<dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st>>>(
-            Buckets{S->table, S->nb}, S->store, row0, n, row0 + n, S->kw, S->count);
-    }
-};
-struct Rehash {
-    Handle* S;
-    const uint64_t* old;
-    int64_t slots;
-    Buckets tb;
-    const uint64_t* store;
-    hipStream_t st;
-    template <int NW>
-    void go() {
-        cache_rehash_kernel<NW + 1><<<dim3((unsigned)((slots + TPB - 1) / TPB)), dim3(TPB), 0, st>>>(
-            old, slots, tb, store, S->rows, S->kw, S->count);
-    }
-};
-struct Lookup {
-    Handle* S;
-    const int32_t* states;
-    int64_t n;
-    int64_t* entry;
-    int32_t *rel, *k;
-    hipStream_t st;
-    template <int NW>
-    void go() {
-        cache_lookup_kernel<NW + 1><<<dim3((unsigned)n), dim3(GT), 0, st>>>(
-            S->view(), states, n, S->L, S->kw, entry, rel, k);
-    }
-};
+// the replay of a call's paths: counting (acx_cache_count) or writing their rows (acx_cache_fill)
+template <bool EMIT>
+static void replay(int L, const FillArgs& a, hipStream_t st) {
+    bfs::by_nw(L, [&](auto nw) {
+        cache_replay_kernel<decltype(nw)::value, EMIT><<<dim3((unsigned)a.P), dim3(GT), 0, st>>>(a);
+    });
+}
 
 static bool fill_args_ok(Handle* S, const int32_t* states, const int64_t* poff, const int32_t* actions, int64_t P) {
     return S && states && poff && actions && P >= 0 && P <= (1ll << 30);
@@ -372,7 +333,7 @@ int acx_cache_count(void* h, const int32_t* states, const int64_t* poff, const i
     if (P == 0) return ACX_OK;
     cache::FillArgs a{states, poff, actions, nullptr, counts, err, nullptr, nullptr, P, 0, 0, 0,
                       S->L, S->kw, cyclical != 0, expand_rotations != 0, replay != 0};
-    by_nw(S->L, cache::Replay{a, false, (hipStream_t)stream});
+    cache::replay<false>(S->L, a, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 
@@ -394,7 +355,11 @@ int acx_cache_reserve(void* h, int64_t rows, void* stream) {
              hipMemcpyAsync(meta, S->meta, 8 * (size_t)S->rows, hipMemcpyDeviceToDevice, st) == hipSuccess;
     if (ok) {  // the entries, codes kept, into the new table; the rehash reads the new store's copy of the keys
         const int64_t slots = (int64_t)S->nb * cache::BUCKET;
-        by_nw(S->L, cache::Rehash{S, S->table, slots, cache::Buckets{table, nb}, store, st});
+        by_nw(S->L, [&](auto nw) {
+            cache::cache_rehash_kernel<decltype(nw)::value + 1>
+                <<<dim3((unsigned)((slots + acx::bfs::TPB - 1) / acx::bfs::TPB)), dim3(acx::bfs::TPB), 0, st>>>(
+                    S->table, slots, cache::Buckets{table, nb}, store, S->rows, S->kw, S->count);
+        });
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
     }
     if (ok) {  // installed only now: a failure above leaves the cache as it was
@@ -427,9 +392,13 @@ int acx_cache_fill(void* h, const int32_t* states, const int64_t* poff, const in
     hipStream_t st = (hipStream_t)stream;
     cache::FillArgs a{states, poff, actions, voff, nullptr, nullptr, S->store, S->meta, P, S->rows, S->cap, ordinal0,
                       S->L, S->kw, cyclical != 0, expand_rotations != 0, replay != 0};
-    by_nw(S->L, cache::Replay{a, true, st});
+    cache::replay<true>(S->L, a, st);
     if (hipGetLastError() != hipSuccess) return ACX_E_LAUNCH;
-    by_nw(S->L, cache::Insert{S, S->rows, total, st});
+    by_nw(S->L, [&](auto nw) {
+        cache::cache_insert_kernel<decltype(nw)::value + 1>
+            <<<dim3((unsigned)((total + acx::bfs::TPB - 1) / acx::bfs::TPB)), dim3(acx::bfs::TPB), 0, st>>>(
+                cache::Buckets{S->table, S->nb}, S->store, S->rows, total, S->rows + total, S->kw, S->count);
+    });
     S->rows += total;
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
@@ -439,7 +408,10 @@ int acx_cache_lookup(void* h, const int32_t* states, int64_t n, int64_t* entry, 
     Handle* S = static_cast<Handle*>(h);
     if (!S || n < 0 || n > (1ll << 30) || (n > 0 && (!states || !entry || !rel || !k))) return ACX_E_ARG;
     if (n == 0) return ACX_OK;
-    by_nw(S->L, cache::Lookup{S, states, n, entry, rel, k, (hipStream_t)stream});
+    by_nw(S->L, [&](auto nw) {
+        cache::cache_lookup_kernel<decltype(nw)::value + 1><<<dim3((unsigned)n), dim3(cache::GT), 0, (hipStream_t)stream>>>(
+            S->view(), states, n, S->L, S->kw, entry, rel, k);
+    });
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 

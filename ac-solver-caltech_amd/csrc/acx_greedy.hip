@@ -510,27 +510,11 @@ struct Engine : Outcome {
     }
 };
 
-struct RoundLaunch {
-    Engine* E;
-    template <int NW>
-    void go() {
-        const int n = E->d.n * ACT;
-        const int cb = (int)((E->d.hi - E->d.lo + 255) / 256);
-        greedy_round_kernel<NW><<<dim3((unsigned)(cb + (n + 255) / 256)), dim3(256), 0, E->stream>>>(E->d, cb);
-    }
-};
-struct CommitLaunch {
-    Engine* E;
-    template <int NW>
-    void go() {
-        const int64_t n = E->d.hi - E->d.lo;
-        greedy_commit_kernel<NW + 1><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, E->stream>>>(E->d);
-    }
-};
-
 void Engine::commit_launch() {
-    CommitLaunch cl{this};
-    bfs::by_nw(L, cl);
+    const int64_t n = d.hi - d.lo;
+    bfs::by_nw(L, [&](auto nw) {
+        greedy_commit_kernel<decltype(nw)::value + 1><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(d);
+    });
 }
 
 int Engine::expand_round(const std::vector<int64_t>& batch) {
@@ -566,8 +550,11 @@ int Engine::expand_round(const std::vector<int64_t>& batch) {
     d.blocks_done = d_blocks;
     d.done_flag = hd_flag;
     d.seq = ++round_seq;
-    RoundLaunch rl{this};
-    bfs::by_nw(L, rl);
+    const int cb = (int)((d.hi - d.lo + 255) / 256);
+    bfs::by_nw(L, [&](auto nw) {
+        greedy_round_kernel<decltype(nw)::value>
+            <<<dim3((unsigned)(cb + (n * ACT + 255) / 256)), dim3(256), 0, stream>>>(d, cb);
+    });
     if (n == 0) return hipGetLastError() == hipSuccess ? wait_round(d.seq) : ACX_E_LAUNCH;
     const int64_t tw = now_ns();
     if (hipGetLastError() != hipSuccess || wait_round(d.seq) != ACX_OK) return ACX_E_LAUNCH;

@@ -185,13 +185,9 @@ __device__ __forceinline__ void begin_body(const Args& a, const cache::Attach& a
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(GT) void mcts_begin_kernel(Args a) {
-    begin_body<NW, false>(a, cache::Attach{});
-}
-template <int NW>
-__global__ __launch_bounds__(GT) void mcts_begin_cached_kernel(Args a, cache::Attach at) {
-    begin_body<NW, true>(a, at);
+template <int NW, class... At>
+__global__ __launch_bounds__(GT) void mcts_begin_kernel(Args a, At... at) {
+    begin_body<NW, sizeof...(At) != 0>(a, cache::attach_of(at...));
 }
 
 template <int NW, bool CACHE>
@@ -385,14 +381,10 @@ __device__ __forceinline__ void select_body(const Args& a, const double* log_tab
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(GT) void mcts_select_kernel(Args a, const double* log_table, int64_t n_log, double c) {
-    select_body<NW, false>(a, log_table, n_log, c, cache::Attach{});
-}
-template <int NW>
-__global__ __launch_bounds__(GT) void mcts_select_cached_kernel(Args a, const double* log_table, int64_t n_log, double c,
-                                                                cache::Attach at) {
-    select_body<NW, true>(a, log_table, n_log, c, at);
+template <int NW, class... At>
+__global__ __launch_bounds__(GT) void mcts_select_kernel(Args a, const double* log_table, int64_t n_log, double c,
+                                                         At... at) {
+    select_body<NW, sizeof...(At) != 0>(a, log_table, n_log, c, cache::attach_of(at...));
 }
 
 __global__ __launch_bounds__(GT) void mcts_backup_kernel(Args a, const float* scores, int64_t M) {
@@ -467,39 +459,6 @@ struct Engine {
 };
 static_assert(sizeof(State) == 56 && scored::RECORD<State> == 140, "the bytes formula of include/acx.h");
 
-struct Begin {
-    const Args& a;
-    hipStream_t st;
-    template <int NW>
-    void go() { mcts_begin_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a); }
-};
-struct Select {
-    const Args& a;
-    hipStream_t st;
-    const double* log_table;
-    int64_t n_log;
-    double c;
-    template <int NW>
-    void go() { mcts_select_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, log_table, n_log, c); }
-};
-struct BeginCached {
-    const Args& a;
-    hipStream_t st;
-    cache::Attach at;
-    template <int NW>
-    void go() { mcts_begin_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at); }
-};
-struct SelectCached {
-    const Args& a;
-    hipStream_t st;
-    const double* log_table;
-    int64_t n_log;
-    double c;
-    cache::Attach at;
-    template <int NW>
-    void go() { mcts_select_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, log_table, n_log, c, at); }
-};
-
 }  // namespace mcts
 }  // namespace acx
 
@@ -519,10 +478,10 @@ void* acx_mcts_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, int
 void acx_mcts_destroy(void* h) { batch::destroy<Engine>(h); }
 
 int acx_mcts_begin(void* h, const int32_t* states, const int64_t* budgets, int64_t n, void* stream) {
-    acx::cache::Attach at;
-    if (h && acx::cache::attached(static_cast<batch::Handle<Engine>*>(h), at))
-        return scored::begin<Engine, mcts::BeginCached>(h, states, budgets, true, n, stream, at);
-    return scored::begin<Engine, mcts::Begin>(h, states, budgets, true, n, stream);
+    return scored::begin<Engine>(h, states, budgets, true, n, stream, [=](auto nw, const mcts::Args& a, auto... at) {
+        mcts::mcts_begin_kernel<decltype(nw)::value>
+            <<<dim3((unsigned)a.n), dim3(mcts::GT), 0, (hipStream_t)stream>>>(a, at...);
+    });
 }
 
 int acx_mcts_set_cache(void* h, void* cache) { return acx::cache::set_cache<batch::Handle<Engine>>(h, cache); }
@@ -533,10 +492,10 @@ int acx_mcts_cache_hits(void* h, int64_t n, int64_t* entry, int32_t* rel, int32_
 
 int acx_mcts_select(void* h, const double* log_table, int64_t n_log, double c_explore, int64_t* pair, void* stream) {
     if (!log_table || n_log < 2 || c_explore != c_explore) return ACX_E_ARG;
-    acx::cache::Attach at;
-    if (h && acx::cache::attached(static_cast<batch::Handle<Engine>*>(h), at))
-        return scored::make<Engine, mcts::SelectCached>(h, pair, stream, log_table, n_log, c_explore, at);
-    return scored::make<Engine, mcts::Select>(h, pair, stream, log_table, n_log, c_explore);
+    return scored::make<Engine>(h, pair, stream, [=](auto nw, const mcts::Args& a, auto... at) {
+        mcts::mcts_select_kernel<decltype(nw)::value>
+            <<<dim3((unsigned)a.n), dim3(mcts::GT), 0, (hipStream_t)stream>>>(a, log_table, n_log, c_explore, at...);
+    });
 }
 
 int acx_mcts_gather(void* h, uint64_t* keys, int64_t M, void* stream) {

@@ -732,39 +732,12 @@ static bool dalloc(T*& p, size_t n) {
 
 static inline int nblocks(int64_t n) { return (int)((n + TPB - 1) / TPB); }
 
-struct ExpandLaunch {
-    Shard* S;
-    hipStream_t st;
-    template <int NW>
-    void go() { sbfs_expand_kernel<NW><<<dim3((unsigned)((S->Pr + STILE - 1) / STILE)), dim3(TPB), 0, st>>>(S->a); }
-};
-struct InsertLaunch {
-    Shard* S;
-    hipStream_t st;
-    template <int NW>
-    void go() { sbfs_insert_kernel<NW + 1><<<dim3(nblocks(12 * (int64_t)S->Pr + S->nrecv)), dim3(TPB), 0, st>>>(S->a); }
-};
-struct RootLaunch {
-    Shard* S;
-    hipStream_t st;
-    RootKey rk;
-    template <int NW>
-    void go() { sbfs_root_kernel<NW + 1><<<dim3(1), dim3(64), 0, st>>>(S->a, rk); }
-};
-
 // the chunk's control block to its initial values (no host copy): at a search's start, and
 // after every chunk's commit read-back (sbfs_publish_kernel)
 __global__ void sbfs_ctl_init_kernel(Ctl* c) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     ctl_init(c);
 }
-struct LookupLaunch {
-    Shard* S;
-    hipStream_t st;
-    int64_t g;
-    template <int NW>
-    void go() { sbfs_lookup_kernel<NW><<<dim3(1), dim3(64), 0, st>>>(S->a, g); }
-};
 
 // the control block published to pinned, coherent host memory by a one-wave kernel (the
 // sequence number written last, system scope) -- a hipMemcpyAsync of it was a ~9 us blit per
@@ -962,9 +935,9 @@ int acx_sbfs_reset(void* h, const int32_t* presentation, void* stream) {
         return ACX_E_LAUNCH;
     sbfs_ctl_init_kernel<<<dim3(1), dim3(64), 0, st>>>(S->a.ctl);
     if (own == S->rank) {
-        RootLaunch rl{S, st, {}};
-        acx::pack_key(presentation, S->L, S->kw, rl.rk.w);
-        by_nw(S->L, rl);
+        RootKey rk{};
+        acx::pack_key(presentation, S->L, S->kw, rk.w);
+        by_nw(S->L, [&](auto nw) { sbfs_root_kernel<decltype(nw)::value + 1><<<dim3(1), dim3(64), 0, st>>>(S->a, rk); });
         S->nloc = 1;
         S->abase = 1;  // the root's record
     }
@@ -996,8 +969,9 @@ int acx_sbfs_expand(void* h, int64_t head, int32_t P, int64_t* out, int32_t read
     // the control block holds its initial values (the search's reset, or the previous chunk's
     // commit read-back re-initialised it)
     if (S->Pr > 0) {
-        ExpandLaunch el{S, st};
-        by_nw(S->L, el);
+        by_nw(S->L, [&](auto nw) {
+            sbfs_expand_kernel<decltype(nw)::value><<<dim3((unsigned)((S->Pr + STILE - 1) / STILE)), dim3(TPB), 0, st>>>(a);
+        });
         sbfs_expand_reduce_kernel<<<dim3(1), dim3(1024), 0, st>>>(a, (S->Pr + STILE - 1) / STILE);
     }
     if (!read_back) return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
@@ -1043,8 +1017,9 @@ int acx_sbfs_insert(void* h, const uint64_t* recv, int64_t nrecv, int64_t end, u
     S->nrecv = nrecv;
     // sslot / lost are SEEN / 0 here: the previous chunk's commit (or the search's reset) cleared them
     if (12 * (int64_t)S->Pr + nrecv > 0) {
-        InsertLaunch il{S, st};
-        by_nw(S->L, il);
+        by_nw(S->L, [&](auto nw) {
+            sbfs_insert_kernel<decltype(nw)::value + 1><<<dim3(nblocks(12 * (int64_t)S->Pr + nrecv)), dim3(TPB), 0, st>>>(S->a);
+        });
     }
     // one rank with no exchange (end < 0): nobody reads gmask before the commit, whose count pass
     // makes the survivor bits itself (sbfs_count_kernel<true>)
@@ -1146,8 +1121,7 @@ int acx_sbfs_lookup(void* h, int64_t g, int64_t* out, void* stream) {
     if (!S || !out) return ACX_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     S->a.nloc = S->nloc;
-    LookupLaunch ll{S, st, g};
-    by_nw(S->L, ll);
+    by_nw(S->L, [&](auto nw) { sbfs_lookup_kernel<decltype(nw)::value><<<dim3(1), dim3(64), 0, st>>>(S->a, g); });
     if (hipGetLastError() != hipSuccess) return ACX_E_LAUNCH;
     if (hipMemcpyAsync(S->look_host, S->a.look, 32, hipMemcpyDeviceToHost, st) != hipSuccess) return ACX_E_LAUNCH;
     if (hipStreamSynchronize(st) != hipSuccess) return ACX_E_LAUNCH;

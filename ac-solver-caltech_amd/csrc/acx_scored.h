@@ -21,6 +21,7 @@
 
 #include "acx_batch.h"
 #include "acx_bfs_common.h"
+#include "acx_cache.h"
 
 namespace acx {
 namespace scored {
@@ -116,11 +117,24 @@ static __global__ __launch_bounds__(TPB) void results_kernel(batch::Args a, int6
 }
 
 // host: the bodies of an engine's acx_*_begin, its make call, _gather, its take call and _finish.
-// A run of n searches begins: own_ok is the engine's check of its own arguments `own`, Launch{args, stream,
-// own...} the by_nw functor of its begin kernel
-template <class E, class Launch, class... Own>
+// The launch of a kernel that probes the solution cache when one is attached to the handle
+// (acx_cache.h): launch(nw, args, at...) starts the kernel's instantiation for decltype(nw)::value
+// key words; `at...` is the handle's attachment or, without one, nothing, and the kernel's `At... at`
+// takes it.  This is the one place that reads the attachment.
+template <class E, class Launch>
+static void launch_by_cache(const batch::Handle<E>* S, Launch launch) {
+    cache::Attach at;
+    if (cache::attached(S, at))
+        by_nw(S->a.L, [&](auto nw) { launch(nw, S->a, at); });
+    else
+        by_nw(S->a.L, [&](auto nw) { launch(nw, S->a); });
+}
+
+// A run of n searches begins: own_ok is the engine's check of its own arguments, launch (above)
+// starts its begin kernel
+template <class E, class Launch>
 static int begin(void* h, const int32_t* states, const int64_t* budgets, bool own_ok, int64_t n, void* stream,
-                 Own... own) {
+                 Launch launch) {
     batch::Handle<E>* S = static_cast<batch::Handle<E>*>(h);
     if (!S || !states || !budgets || !own_ok || n < 0 || n > S->n_cap) return ACX_E_ARG;
     typename E::Args& a = S->a;
@@ -130,20 +144,19 @@ static int begin(void* h, const int32_t* states, const int64_t* budgets, bool ow
     if (!batch::new_epoch(S, st)) return ACX_E_LAUNCH;
     a.states = states;
     a.budgets = budgets;
-    by_nw(a.L, Launch{a, st, own...});
+    launch_by_cache(S, launch);
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 
-// the first half of a step: the engine's kernel (Launch{args, stream, own...}, `own` the engine's
-// own arguments of the call: mcts) over the live searches, then the offsets; out takes M (and, for
-// an engine with LIVE, the live count)
-template <class E, class Launch, class... Own>
-static int make(void* h, int64_t* out, void* stream, Own... own) {
+// the first half of a step: the engine's kernel (launch, as above) over the live searches, then the
+// offsets; out takes M (and, for an engine with LIVE, the live count)
+template <class E, class Launch>
+static int make(void* h, int64_t* out, void* stream, Launch launch) {
     batch::Handle<E>* S = static_cast<batch::Handle<E>*>(h);
     if (!S || !out) return ACX_E_ARG;
     const typename E::Args& a = S->a;
     hipStream_t st = (hipStream_t)stream;
-    if (a.n > 0) by_nw(a.L, Launch{a, st, own...});
+    if (a.n > 0) launch_by_cache(S, launch);
     offsets_kernel<typename E::Args, E::LIVE><<<dim3(1), dim3(1024), 0, st>>>(a, out);
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }

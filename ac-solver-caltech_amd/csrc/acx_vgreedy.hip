@@ -75,11 +75,12 @@
 // then the cache, then the visited set -- one wave-wide probe per child.  A hit ends the search with
 // ACX_BFS_CACHED, the nodes of a found search and min_length 2; the path reader returns the path to
 // the popped node plus the child's (action, total), and the hit record (entry, rel, k) goes to the
-// attachment's array, not to the search's slice.  vgreedy_pop_cached_kernel<1 / 2 / 3 / 4 / 8>:
-// 53 / 55 / 57 / 59 / 68 VGPRs, the same LDS (profiles/cache/kernel_resources.md).
+// attachment's array, not to the search's slice.  vgreedy_pop_kernel<1 / 2 / 3 / 4 / 8, cache::Attach>:
+// 53 / 55 / 57 / 59 / 68 VGPRs, the same LDS (profiles/cache/kernel_resources.md, where its
+// name has _cached before _kernel).
 //
 // Fused with the FeatureMLP scorer (acx_vgreedy_run_mlp; acx_mlp.h, acx_feat.h): the pop and push
-// kernels' bodies are device functions, and vgreedy_fused_kernel<NW> / vgreedy_fused_cached_kernel<NW>
+// kernels' bodies are device functions, and vgreedy_fused_kernel<NW> / vgreedy_fused_kernel<NW, cache::Attach>
 // loop them in one launch, up to max_pops times per search, with the scorer between them on the
 // device: 4 candidates at a time, lane c computes candidate c's 14 features from its store row
 // (acx_features' arithmetic, normalisation included) into LDS, the wave runs the layers, and lane c
@@ -89,8 +90,9 @@
 // fused calls may alternate on a handle.
 // vgreedy_fused_kernel<1 / 2 / 3 / 4 / 8>   126 / 128 / 130 / 132 / 169 VGPRs, 4,432 / 4,528 / 4,624 /
 //       4,720 / 5,104 B of LDS (the pop's + 4,096 B of activations + 48 B of scores), no scratch but
-//       <2>'s 24 B, which are pop_body<2>'s; vgreedy_fused_cached_kernel 128 / 133 / 166 / 167 / 171
-//       VGPRs, the same LDS (profiles/fused_mlp/kernel_resources.md).
+//       <2>'s 24 B, which are pop_body<2>'s; vgreedy_fused_kernel<.., cache::Attach> 128 / 133 / 166 / 167 /
+//       171 VGPRs, the same LDS (profiles/fused_mlp/kernel_resources.md, where its name
+//       has _cached before _kernel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -167,13 +169,9 @@ __device__ __forceinline__ void begin_body(const Args& a, const cache::Attach& a
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(GT) void vgreedy_begin_kernel(Args a) {
-    begin_body<NW, false>(a, cache::Attach{});
-}
-template <int NW>
-__global__ __launch_bounds__(GT) void vgreedy_begin_cached_kernel(Args a, cache::Attach at) {
-    begin_body<NW, true>(a, at);
+template <int NW, class... At>
+__global__ __launch_bounds__(GT) void vgreedy_begin_kernel(Args a, At... at) {
+    begin_body<NW, sizeof...(At) != 0>(a, cache::attach_of(at...));
 }
 
 template <int NW, bool CACHE>
@@ -288,13 +286,9 @@ __device__ __forceinline__ void pop_body(const Args& a, const cache::Attach& at)
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(GT) void vgreedy_pop_kernel(Args a) {
-    pop_body<NW, false>(a, cache::Attach{});
-}
-template <int NW>
-__global__ __launch_bounds__(GT) void vgreedy_pop_cached_kernel(Args a, cache::Attach at) {
-    pop_body<NW, true>(a, at);
+template <int NW, class... At>
+__global__ __launch_bounds__(GT) void vgreedy_pop_kernel(Args a, At... at) {
+    pop_body<NW, sizeof...(At) != 0>(a, cache::attach_of(at...));
 }
 
 // The push kernel's body: the scores of search q's candidates are scores[off ..], off the search's
@@ -410,16 +404,13 @@ __device__ __forceinline__ void fused_body(const Args& a, const cache::Attach& a
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(GT) void vgreedy_fused_kernel(Args a, mlp::Net net, const float* mean, const float* stdv,
-                                                           int64_t max_pops, unsigned long long* pair) {
-    fused_body<NW, false>(a, cache::Attach{}, net, mean, stdv, max_pops, pair);
-}
-template <int NW>
-__global__ __launch_bounds__(GT) void vgreedy_fused_cached_kernel(Args a, cache::Attach at, mlp::Net net,
-                                                                  const float* mean, const float* stdv,
-                                                                  int64_t max_pops, unsigned long long* pair) {
-    fused_body<NW, true>(a, at, net, mean, stdv, max_pops, pair);
+// (the attachment is the second argument, as it was when this kernel had a twin: a pack that is
+// not last is not deduced, so the launch names it -- vgreedy_fused_kernel<NW, decltype(at)...>)
+template <int NW, class... At>
+__global__ __launch_bounds__(GT) void vgreedy_fused_kernel(Args a, At... at, mlp::Net net, const float* mean,
+                                                           const float* stdv, int64_t max_pops,
+                                                           unsigned long long* pair) {
+    fused_body<NW, sizeof...(At) != 0>(a, cache::attach_of(at...), net, mean, stdv, max_pops, pair);
 }
 
 // what the handle (acx_batch.h) and the step frame (acx_scored.h) need of this engine
@@ -441,59 +432,6 @@ struct Engine {
 };
 static_assert(sizeof(State) == 56 && scored::RECORD<State> == 140, "the bytes formula of include/acx.h");
 
-struct Begin {
-    const Args& a;
-    hipStream_t st;
-    template <int NW>
-    void go() { vgreedy_begin_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a); }
-};
-struct Pop {
-    const Args& a;
-    hipStream_t st;
-    template <int NW>
-    void go() { vgreedy_pop_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a); }
-};
-struct BeginCached {
-    const Args& a;
-    hipStream_t st;
-    cache::Attach at;
-    template <int NW>
-    void go() { vgreedy_begin_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at); }
-};
-struct PopCached {
-    const Args& a;
-    hipStream_t st;
-    cache::Attach at;
-    template <int NW>
-    void go() { vgreedy_pop_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at); }
-};
-
-struct Fused {
-    const Args& a;
-    hipStream_t st;
-    mlp::Net net;
-    const float *mean, *stdv;
-    int64_t max_pops;
-    unsigned long long* pair;
-    template <int NW>
-    void go() {
-        vgreedy_fused_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, net, mean, stdv, max_pops, pair);
-    }
-};
-struct FusedCached {
-    const Args& a;
-    hipStream_t st;
-    cache::Attach at;
-    mlp::Net net;
-    const float *mean, *stdv;
-    int64_t max_pops;
-    unsigned long long* pair;
-    template <int NW>
-    void go() {
-        vgreedy_fused_cached_kernel<NW><<<dim3((unsigned)a.n), dim3(GT), 0, st>>>(a, at, net, mean, stdv, max_pops, pair);
-    }
-};
-
 }  // namespace vgreedy
 }  // namespace acx
 
@@ -513,17 +451,17 @@ void* acx_vgreedy_create(int32_t L, int64_t n_searches, int64_t max_nodes_each, 
 void acx_vgreedy_destroy(void* h) { batch::destroy<Engine>(h); }
 
 int acx_vgreedy_begin(void* h, const int32_t* states, const int64_t* budgets, int64_t n, void* stream) {
-    acx::cache::Attach at;
-    if (h && acx::cache::attached(static_cast<batch::Handle<Engine>*>(h), at))
-        return scored::begin<Engine, vgreedy::BeginCached>(h, states, budgets, true, n, stream, at);
-    return scored::begin<Engine, vgreedy::Begin>(h, states, budgets, true, n, stream);
+    return scored::begin<Engine>(h, states, budgets, true, n, stream, [=](auto nw, const vgreedy::Args& a, auto... at) {
+        vgreedy::vgreedy_begin_kernel<decltype(nw)::value>
+            <<<dim3((unsigned)a.n), dim3(vgreedy::GT), 0, (hipStream_t)stream>>>(a, at...);
+    });
 }
 
 int acx_vgreedy_pop(void* h, int64_t* pair, void* stream) {
-    acx::cache::Attach at;
-    if (h && acx::cache::attached(static_cast<batch::Handle<Engine>*>(h), at))
-        return scored::make<Engine, vgreedy::PopCached>(h, pair, stream, at);
-    return scored::make<Engine, vgreedy::Pop>(h, pair, stream);
+    return scored::make<Engine>(h, pair, stream, [=](auto nw, const vgreedy::Args& a, auto... at) {
+        vgreedy::vgreedy_pop_kernel<decltype(nw)::value>
+            <<<dim3((unsigned)a.n), dim3(vgreedy::GT), 0, (hipStream_t)stream>>>(a, at...);
+    });
 }
 
 int acx_vgreedy_set_cache(void* h, void* cache) { return acx::cache::set_cache<batch::Handle<Engine>>(h, cache); }
@@ -553,11 +491,10 @@ int acx_vgreedy_run_mlp(void* h, const float* params, const int32_t* dims, int32
     if (hipMemsetAsync(out, 0, 16, st) != hipSuccess) return ACX_E_LAUNCH;
     if (a.n == 0) return ACX_OK;
     const acx::mlp::Net net = acx::mlp::net_of(params, dims, n_layers);
-    acx::cache::Attach at;
-    if (acx::cache::attached(S, at))
-        acx::bfs::by_nw(a.L, vgreedy::FusedCached{a, st, at, net, mean, stdv, max_pops, out});
-    else
-        acx::bfs::by_nw(a.L, vgreedy::Fused{a, st, net, mean, stdv, max_pops, out});
+    scored::launch_by_cache(S, [=](auto nw, const vgreedy::Args& a, auto... at) {
+        vgreedy::vgreedy_fused_kernel<decltype(nw)::value, decltype(at)...>
+            <<<dim3((unsigned)a.n), dim3(vgreedy::GT), 0, st>>>(a, at..., net, mean, stdv, max_pops, out);
+    });
     return hipGetLastError() == hipSuccess ? ACX_OK : ACX_E_LAUNCH;
 }
 

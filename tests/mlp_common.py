@@ -1,5 +1,5 @@
 """What the tests of acx.DeviceMLP share (test_mlp_host.py, test_gpu_mlp_scores.py,
-test_gpu_fused_vgreedy.py, weak_hash_mlp_child.py): the seeded networks, a float64 evaluation with its
+test_gpu_fused_vgreedy.py, weak_hash_child.py): the seeded networks, a float64 evaluation with its
 error bound, and the searches of the fused value-guided greedy search with the yardstick's answers."""
 import functools
 

@@ -3,21 +3,15 @@ acx.beam_search[_many] and acx.mcts_search[_many] on the GPU, against the refere
 (tests/golden/cache_dicts.npz, cache_search.json: make_golden_cache.py) and, where the fixture has no
 record, against the yardstick that reproduces them (tests/cache_yardstick.py, test_cache_cpu.py).
 Every comparison is exact: keys, values -- and so which path won a state --, paths, node counts."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 import cache_yardstick as CY
 from oracle import oracle as O
-from conftest import REPO
-from scored_common import _FnModel
+from scored_common import AK3, _FnModel, _pad
 from test_cache_cpu import cache_of, dict_of, inputs_of, load_dicts, load_records
-from weak_hash_common import FATAL, variant
+from weak_hash_common import ChildDied, run_child, skip_after_death
 
 pytestmark = pytest.mark.gpu
 
@@ -26,6 +20,12 @@ FOUND, BUDGET, CACHED = 1, 2, 4
 ENGINES = ["vgreedy", "mcts", "beam"]
 STAT = {"vgreedy": "min_length", "mcts": "iterations", "beam": "steps"}  # a record's third stat, and the stats dict's key
 BEAM_W = 5  # the beam records' width (make_golden_cache.py)
+DEAD = []  # why the weak-hash child died: the tests after it are skipped
+
+
+@pytest.fixture(autouse=True)
+def _one_death_ends_the_module():
+    skip_after_death(DEAD)
 
 
 @pytest.fixture(scope="module")
@@ -352,6 +352,62 @@ def test_beam_hit_in_the_second_pass_and_with_keys_in_scratch(z):
 
 
 # ---------------------------------------------------------------------------------------------
+# every key-word instantiation of the cached begin and make kernels
+# ---------------------------------------------------------------------------------------------
+def first_child_case(L):
+    """AK(3) padded to L, and a cache of one entry that the child of the root's first eligible action
+    a meets through a rotation: -> (root, a, the child's total, the cache's dict, the path
+    cache_yardstick.check returns for the child).  The entry's key is the child with relator 1
+    rotated left by one letter; a is the first action whose child does not raise, is not trivial
+    and is found, while the root and no earlier child raises, is trivial or is found."""
+    root = _pad(AK3, L)
+    children = [O.move(root, L, a, False) for a in range(12)]
+    for a, (child, lens, err) in enumerate(children):
+        if err != 0 or sum(lens) == 2:
+            continue
+        r1 = child[L:][child[L:] != 0]
+        key = child.copy()
+        key[L:L + len(r1)] = np.concatenate([r1[1:], r1[:1]])
+        d = {tuple(int(x) for x in key): [(5, 9)]}
+        hit = CY.check(child, L, d)
+        if hit is None or CY.check(root, L, d) is not None:
+            continue
+        if all(e == 0 and sum(ln) != 2 and CY.check(c, L, d) is None for c, ln, e in children[:a]):
+            assert hit[1:] == (1, 1) and len(hit[0]) == 2  # one rotation move, then the cached path
+            return root, a, sum(lens), d, hit[0]
+    raise AssertionError(f"no action of AK(3) at L = {L} has such a child")
+
+
+def _one(engine, p, cache):
+    import acx
+    kw = dict(device=DEV, return_stats=True, solution_cache=cache)
+    if engine == "beam":
+        return acx.beam_search_many(p[None], _length, BEAM_W, 50, False, **kw)
+    if engine == "vgreedy":
+        return acx.value_guided_greedy_search_many(p[None], _length, 50, False, **kw)
+    return acx.mcts_search_many(p[None], _zero, 50, 1.0, False, **kw)
+
+
+@pytest.mark.parametrize("L", [16, 17, 33, 49, 65])
+@pytest.mark.parametrize("engine", ENGINES)
+def test_cached_kernels_at_every_key_word_count(engine, L):
+    """one L per key-word class (1, 2, 3, 4 and 8 words) and both sides of the first boundary: the
+    cached begin kernel misses the root and the cached make kernel hits the first pop's, pass's or
+    expansion's child a; then the root itself hits; then the same handle searches without a cache.
+    The expectation is oracle.move's and cache_yardstick.check's alone."""
+    import acx
+    root, a, total, d, tail = first_child_case(L)
+    res, st = _one(engine, root, acx.SolutionCache.from_dict(d, L, DEV))
+    assert res == [(True, [(a, total)] + tail)]
+    assert st["status"][0] == CACHED and bool(st["cache_hit"][0])
+    at_root = {tuple(int(x) for x in root): [(5, 9)]}
+    res, st = _one(engine, root, acx.SolutionCache.from_dict(at_root, L, DEV))
+    assert res == [(True, CY.check(root, L, at_root)[0])] and st["nodes"][0] == 1 and st["status"][0] == CACHED
+    res, st = _one(engine, root, None)
+    assert "cache_hit" not in st and CACHED not in st["status"]
+
+
+# ---------------------------------------------------------------------------------------------
 # under the colliding hash
 # ---------------------------------------------------------------------------------------------
 def test_weak_hash(z, tmp_path):
@@ -365,16 +421,13 @@ def test_weak_hash(z, tmp_path):
         CY.backfill(y, p, path)
     recs = [r for r in load_records() if r["engine"] == "vgreedy" and r["cache"] == "U" and r["budget"] == 600][:12]
     queries = z["q_states"][::9]
-    job = dict(L=18, presentations=pres.tolist(), paths=[[list(m) for m in p] for p in paths],
+    job = dict(op="cache", L=18, presentations=pres.tolist(), paths=[[list(m) for m in p] for p in paths],
                queries=queries.tolist(), searches=[r["presentation"] for r in recs], budget=150)
-    with open(tmp_path / "in.json", "w") as f:
-        json.dump(job, f)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "cache_weak_child.py"), str(tmp_path)],
-                       env=dict(os.environ, ACX_LIB=variant()), capture_output=True, text=True, timeout=240)
-    if r.returncode < 0 or r.returncode in FATAL:
-        pytest.fail(f"the weak-hash child died with exit code {r.returncode}: {r.stderr[-2000:]}")
-    assert r.returncode == 0, r.stderr[-4000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    try:
+        (out,), _, _ = run_child([job], tmp_path, timeout=240)
+    except ChildDied as e:
+        DEAD.append(f"test_weak_hash: {e}")
+        pytest.fail(DEAD[-1])
     assert out["classes"] == 8 and out["capacity"] > 64
     got = {tuple(k): [tuple(m) for m in v] for k, v in zip(out["keys"], out["values"])}
     _same_dict(got, y)

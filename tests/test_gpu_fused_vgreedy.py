@@ -12,6 +12,7 @@ import torch
 
 import mlp_common as MC
 import vgreedy_yardstick as Y
+import weak_hash_common as W
 from many_common import _norm, _same
 from scored_common import AK3, SENTINEL, _pad, _refused
 from test_gpu_batch_refusals import _check_search as _refusals_check_search
@@ -22,6 +23,12 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 NARROW = (64,)
 WIDE = (256, 256, 128)
+DEAD = []  # why the weak-hash child died: the tests after it are skipped
+
+
+@pytest.fixture(autouse=True)
+def _one_death_ends_the_module():
+    W.skip_after_death(DEAD)
 
 
 def _many(L, kind, hidden, cyc, **kw):
@@ -224,13 +231,10 @@ def test_refused_searches_through_the_c_abi(L):
             _refusals_check_search(out, i, ys[i // 6], ("status", "nodes", "steps", "min_length"))
 
 
-def test_through_the_weak_hash_library(tmp_path, monkeypatch):
+def test_through_the_weak_hash_library(tmp_path):
     """one case of the comparison with the yardstick through libacx_weakhash.so (8 hash classes: every
     insert of the visited set meets other states' entries): a fresh process, as
     tests/weak_hash_child.py runs the other engines"""
-    import os
-    import weak_hash_common as W
-    monkeypatch.setattr(W, "CHILD", os.path.join(os.path.dirname(W.CHILD), "weak_hash_mlp_child.py"))
     L, kind, cyc = 17, "length", False
     pres, budgets = MC.search_case(L)
     calls = [dict(op="vgreedy_mlp_many", pres=pres.tolist(), budgets=list(budgets), cyc=cyc, kind=kind,
@@ -238,7 +242,8 @@ def test_through_the_weak_hash_library(tmp_path, monkeypatch):
     try:
         (fused, stepped), _, _ = W.run_child(calls, tmp_path, timeout=120)
     except W.ChildDied as e:
-        pytest.fail(f"the weak-hash child died: {e}")
+        DEAD.append(f"the weak-hash child died: {e}")
+        pytest.fail(DEAD[-1])
     want = _many(L, kind, NARROW, cyc)
     for got in (fused, stepped):
         assert got["res"] == want[0]

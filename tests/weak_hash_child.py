@@ -1,5 +1,5 @@
-"""The process that runs a job of tests/test_gpu_weak_hash.py or tests/test_weak_hash_cpu.py through
-libacx_weakhash.so (ac-solver-caltech_amd/build.py; the key hash of csrc/acx_test_hash.h with 8
+"""The process that runs a job of tests/test_gpu_weak_hash.py, tests/test_weak_hash_cpu.py,
+tests/test_gpu_cache.py or tests/test_gpu_fused_vgreedy.py through libacx_weakhash.so (ac-solver-caltech_amd/build.py; the key hash of csrc/acx_test_hash.h with 8
 classes): the variant cannot share a process with libacx.so, so each job gets a fresh one.
 
     ACX_LIB=<variant> python tests/weak_hash_child.py <dir>
@@ -145,6 +145,20 @@ class Ops:
                                  lambda p, j: Y.vgreedy(p, c["scorer"], c["budgets"][j], c["cyc"], drop_twins=True),
                                  scorer=Y.SCORERS[c["scorer"]][1], max_nodes_to_explore=c["budgets"])
 
+    def vgreedy_mlp_many(self, i, c):
+        """acx.value_guided_greedy_search_many scored by the acx.DeviceMLP mlp_common.net(kind, hidden)
+        with its normalisation, fused or stepped; the nodes whose key hashes are counted are the
+        yardstick's, scored by mlp.host"""
+        import acx
+        import mlp_common as MC
+        import vgreedy_yardstick as Y
+        mlp, mean, std = MC.net(c["kind"], tuple(c["hidden"]))
+        return self._scored_many(acx.value_guided_greedy_search_many, c,
+                                 lambda p, j: Y.vgreedy(p, mlp.host, c["budgets"][j], c["cyc"], mean=mean, std=std,
+                                                        drop_twins=True),
+                                 scorer=mlp, max_nodes_to_explore=c["budgets"], feat_mean=mean, feat_std=std,
+                                 fused=c["fused"])
+
     def mcts_many(self, i, c):
         """scorer: a name of mcts_yardstick.MODELS or TOKEN_MODELS, taken as the value itself"""
         import acx
@@ -155,6 +169,27 @@ class Ops:
                                                      on_tokens=tokens),
                                  scorer=Y.model_t(c["scorer"]), scorer_input="tokens" if tokens else "features",
                                  max_nodes_to_explore=c["budgets"], c_explore=c["c"])
+
+    def cache(self, i, c):
+        """the solution cache: {"L", "presentations", "paths", "queries", "searches", "budget"} -> the
+        classes of the variant's hash, the cache's dict after a backfill in two calls from a capacity
+        of 64 (as lists), the paths_for of every query, and the value-guided greedy searches with the
+        cache attached"""
+        import acx
+        k = acx.SolutionCache(c["L"], self.dev, capacity=64)
+        paths = [[tuple(m) for m in p] for p in c["paths"]]
+        half = len(paths) // 2
+        k.backfill_many(np.array(c["presentations"][:half]), paths[:half])
+        k.backfill_many(np.array(c["presentations"][half:]), paths[half:])
+        d = k.to_dict()
+        found = k.paths_for(np.array(c["queries"]))
+        res, st = acx.value_guided_greedy_search_many(np.array(c["searches"]), lambda f: f[:, 0], c["budget"],
+                                                      device=self.dev, solution_cache=k, return_stats=True)
+        return dict(classes=int(self.lib.acx_internal_hash_classes()), entries=len(k), capacity=k.capacity,
+                    keys=[list(x) for x in d], values=[[list(m) for m in v] for v in d.values()],
+                    found=[None if p is None else [list(m) for m in p] for p in found],
+                    results=[[bool(ok), [list(m) for m in p]] for ok, p in res],
+                    nodes=st["nodes"].tolist(), cache_hit=st["cache_hit"].tolist())
 
     def sbfs(self, i, c):
         """arena_log2_cap: on a fresh workspace whose key arena starts at 2^cap records (the

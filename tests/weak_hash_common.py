@@ -1,5 +1,5 @@
-"""What tests/test_weak_hash_cpu.py and tests/test_gpu_weak_hash.py share: where the variant library
-is, how a job is handed to tests/weak_hash_child.py, and the key packer."""
+"""What tests/test_weak_hash_cpu.py, tests/test_gpu_weak_hash.py and the weak-hash tests of
+tests/test_gpu_cache.py and tests/test_gpu_fused_vgreedy.py share: where the variant library is, how a job is handed to tests/weak_hash_child.py, and the key packer."""
 import json
 import os
 import subprocess
