@@ -9,11 +9,12 @@ EXHAUSTED, FOUND, BUDGET, MOVE_ERROR = 0, 1, 2, 3  # ACX_BFS_* of include/acx.h
 ROUND = 64  # parents a round of csrc/acx_mbfs.hip takes at most
 
 
-def bfs(presentation, max_nodes, cyclical=False, ahead=256):
+def bfs(presentation, max_nodes, cyclical=False, ahead=256, states=False):
     """dict: status, ok, path, raises, nodes (len(tree_nodes) at the ending event), parents
     expanded, min_length, and for the tests that need the search's shape: nodes_after[i] =
     len(tree_nodes) after parent i, node_parent[j] = the parent that appended node j, dups =
-    (parent, node it met again) per child whose state was already seen."""
+    (parent, node it met again) per child whose state was already seen.  With states=True also
+    states = tree_nodes itself, an (n, 2L) int32 array in the order the nodes were stored."""
     start = np.asarray(presentation, np.int32)
     L = len(start) // 2
     nodes, seen, node_parent = [start], {start.tobytes(): 0}, [-1]
@@ -50,6 +51,8 @@ def bfs(presentation, max_nodes, cyclical=False, ahead=256):
         at += 1
     out.update(nodes=len(nodes), parents=at, min_length=min_length, nodes_after=nodes_after,
                node_parent=node_parent, dups=dups)
+    if states:
+        out["states"] = np.stack(nodes)
     return out
 
 

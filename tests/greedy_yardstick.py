@@ -19,12 +19,16 @@ def greedy(presentation, max_nodes, cyclical=False, shape=False):
     frontier_after[i] = len(to_explore) then, same_child = pops that yield one new child twice,
     k0_ties (with shape=True: it scans the frontier at every pop) = pops at which another frontier
     node shares the popped node's total, path length and first 8 letters, success_beats_cut = the
-    success came in a pop whose earlier children had already met the budget."""
+    success came in a pop whose earlier children had already met the budget.  With shape=True
+    also runner_up[i] = the (total, path length, state) of the frontier's second entry in heap
+    order at pop i (None when the popped node was alone), and stored = the states of tree_nodes in
+    the order they were added."""
     start = np.asarray(presentation, np.int32)
     L = len(start) // 2
     total0 = int(np.count_nonzero(start))
     heap = [(total0, 0, tuple(int(x) for x in start), [(-1, total0)])]
     seen = {heap[0][2]}
+    stored, runner_up = [heap[0][2]], []
     min_length = total0
     out = dict(status=EXHAUSTED, ok=False, path=None, raises=False, success_beats_cut=False)
     pops, nodes_after, frontier_after, same_child, k0_ties = [], [], [], [], []
@@ -33,6 +37,8 @@ def greedy(presentation, max_nodes, cyclical=False, shape=False):
         top = heap[0]
         if shape and any(e is not top and e[:2] == top[:2] and e[2][:8] == top[2][:8] for e in heap):
             k0_ties.append(len(pops))
+        if shape:
+            runner_up.append(min((e[:3] for e in heap if e is not top), default=None))
         _, depth, state, path = heapq.heappop(heap)
         pops.append(state)
         ch, lens, err = (x[0] for x in O.expand12(np.array([state], np.int32), L, cyclical))
@@ -53,6 +59,8 @@ def greedy(presentation, max_nodes, cyclical=False, shape=False):
             if key not in seen:
                 seen.add(key)
                 new.add(key)
+                if shape:
+                    stored.append(key)
                 heapq.heappush(heap, (total, depth + 1, key, path + [(a, total)]))
         else:
             nodes_after.append(len(seen))
@@ -63,4 +71,6 @@ def greedy(presentation, max_nodes, cyclical=False, shape=False):
         out["path"] = path + [(a, total)]  # greedy.py:121
     out.update(nodes=len(seen), parents=len(pops), min_length=min_length, pops=pops, nodes_after=nodes_after,
                frontier_after=frontier_after, same_child=same_child, k0_ties=k0_ties)
+    if shape:
+        out.update(runner_up=runner_up, stored=stored)
     return out

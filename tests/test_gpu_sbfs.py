@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, PKG_ROOT, REPO
+from conftest import GOLDEN, PKG_ROOT, REPO, unpack_keys_np
 
 pytestmark = pytest.mark.gpu
 
@@ -173,6 +173,13 @@ def test_sharded_bfs_multi_rank(world):
               "ak2": ([1, 1, -2, -2, -2, 0, 0, 1, 2, 1, -2, -1, -2, 0], 10 ** 6, False, 64),
               # a start whose search finds new minima (the verbose trace crosses the ranks)
               "ms17": (_ms17(), 60_000, False, 3000)}
+    edge = {}
+    if world == 2:  # near-full starts whose keys have 4 and 5 words (tests/search_edge_common.py), budget 300, chunk 3
+        import search_edge_common as SE
+        for name, L in (("N1", 49), ("N0", 64)):
+            case = SE.cases(L, False)[name]
+            edge[f"edge_{name}_{L}"] = (L, SE.mid_run(case, "bfs"))
+            orders[f"edge_{name}_{L}"] = (case["start"].tolist(), case["mid"], False, 3)
     cases = _extra_cases(40)
     jobs = {"orders": orders, "cases": cases, "case_chunk": 3}
     ctx = mp.get_context("spawn")
@@ -209,6 +216,9 @@ def test_sharded_bfs_multi_rank(world):
         assert n >= min(nd, 1) and len(ids) >= n and np.unique(ids).size == len(ids), name
         assert np.array_equal(ids[:n], np.arange(n)), name
         assert np.array_equal(keys[:n], dk), name
+        if name in edge:  # and the yardstick's states, node for node
+            L, y = edge[name]
+            assert nd == y["nodes"] and np.array_equal(unpack_keys_np(keys[:nd], L), y["states"]), name
 
 
 _RCCL_SCRIPT = r"""

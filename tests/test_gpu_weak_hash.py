@@ -314,6 +314,51 @@ def test_mcts_many(tmp_path):
     assert large >= 12
 
 
+def test_edge_lengths(tmp_path):
+    """The near-full starts of tests/search_edge_common.py at L = 49 (the first L of NW = 4) and
+    L = 64 (its full tile: 5 key words), both flags, at their three budgets, through the device
+    BFS (chunk 3), the device greedy and the two batched engines: the yardsticks' values.  Twins
+    that differ in the top key word of a relator's tile share a chain with every other node here,
+    so the compare over all the key's words alone keeps them apart."""
+    import search_edge_common as SE
+    from conftest import unpack_keys_np
+    calls, want = [], []
+    for L in (49, 64):
+        for cyc in (False, True):
+            cs = [SE.cases(L, cyc)[name] for name in ("N1", "N0")]
+            for c in cs:
+                for budget, y in c["bfs"]:
+                    calls.append({"op": "device_bfs", "pres": c["start"].tolist(), "budget": int(budget), "cyc": cyc,
+                                  "chunk": 3, "keys": True})
+                    want.append(("device_bfs", L, y))
+                for budget, y in c["greedy"]:
+                    calls.append({"op": "greedy_device", "pres": c["start"].tolist(), "budget": int(budget), "cyc": cyc,
+                                  "keys": True})
+                    want.append(("greedy_device", L, y))
+            for op, engine in (("bfs_many", "bfs"), ("greedy_many", "greedy")):
+                part = [(c["start"], b, y) for c in cs for b, y in c[engine]]
+                calls.append({"op": op, "pres": [p[0].tolist() for p in part], "budgets": [int(p[1]) for p in part],
+                              "cyc": cyc})
+                want.append((op, L, part))
+    out, arrays = _job("edge_lengths", calls, tmp_path)
+    for i, ((op, L, y), a) in enumerate(zip(want, out)):
+        tag = (i, op, L)
+        if op in ("bfs_many", "greedy_many"):
+            _check_many(a, [(p[0], p[2]) for p in y], tag)
+            continue
+        assert not y["raises"] and not a.get("raises"), tag
+        path = None if y["path"] is None else [list(x) for x in y["path"]]
+        assert (a["ok"], a["min_length"]) == (y["ok"], y["min_length"]) and 1 <= a["classes"] <= 8, tag
+        if y["status"] == YB.BUDGET:
+            assert a["nodes"] == y["nodes"], tag
+        if op == "device_bfs":
+            assert (a["status"], a["parents"], a["path"]) == (y["status"], y["parents"], path), tag
+            keys = arrays[f"a{i}_keys"]
+            assert len(keys) >= y["nodes"] and np.array_equal(unpack_keys_np(keys[:y["nodes"]], L), y["states"]), tag
+        else:  # acx_greedy_status: 1 success, 2 failed
+            assert (a["status"], a["path"]) == (1 if y["ok"] else 2, path), tag
+
+
 # ---------------------------------------------------------------------------------------------
 # the device greedy (csrc/acx_greedy.hip: host_hash, Recent, read-only probe / CAS-only commit)
 # ---------------------------------------------------------------------------------------------
